@@ -1,7 +1,20 @@
 #!/usr/bin/env python
 """Headline bench of the encoder hot path (BASELINE.json metric / SURVEY.md section 8d).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times K steps, writes the last timed step's outputs if --dump-outputs is
+given, and prints the result line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  --full adds the
+side measurements after the timed region: the padded-row and forward-only rates, the B = 64 forward and B = 36 step
+(fwd_b64, b36), the collective block for N > 1, the per-kernel timing and roofline, and the CPU oracle baseline with
+its HIP-vs-oracle differences.  Without --full their fields are null.
+
+--dump-outputs DIR: what the timed path handed its caller in the last timed step, as DIR/<name>.npy (float32): in train
+mode the reference's 7-tuple (loss.npy, mask_loss.npy, ...) and a fixed sample of every parameter and its gradient
+after the step (params_sample.npy, grads_sample.npy); in fwd mode sequence_output.npy and pooled_output.npy.  Outputs of
+more than DUMP_MAX_ELEMS elements in all are cut to fit: the larger arrays become fixed seeded samples.  The weights
+(seed 0), the batch (seed 1234 + rank) and the dropout seeds depend on the arguments only, so two builds can be compared
+output for output.
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (RANK / WORLD_SIZE in
 the environment, one rank per GPU), or started plainly -- then this process starts that launcher itself as a CHILD
@@ -14,8 +27,8 @@ A step = one pass of the hot path over one synthetic batch that is already resid
                 bf16 compute, B=256 x (128 text + 100 region) per GPU [BASELINE configs[2]], weak scaling
   --mode fwd    BertImgModelwithLocationEmbeds.forward (embeddings + region projection + 12-layer
                 encoder + pooler), same shapes   [BASELINE configs[1]]
-The train-mode line also carries the forward-only rate measured in the same process.
-Prints ONE JSON line (rank 0) with whole-job samples/s, the live per-kernel roofline of the
+With --full the train-mode line also carries the forward-only rate measured in the same process.
+Prints ONE JSON line (rank 0) with whole-job samples/s; with --full also the live per-kernel roofline of the
 dominant kernel (the MFMA GEMM), and -- at N=1 -- the CPU oracle timed on the host cores.
 """
 import argparse
@@ -83,11 +96,16 @@ def main():
     ap.add_argument("--dropout", type=float, default=0.1,
                     help="hidden / attention-probs dropout in the train step (reference defaults: --drop_out 0.1, "
                          "params.py:299, and BERT-base attention_probs_dropout_prob 0.1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements after the timed region (padded-row and forward-only rates, "
+                         "fwd_b64, b36, collective, per-kernel timing / roofline, CPU oracle baseline); off: their fields are null")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the per-kernel timing")
     ap.add_argument("--no-fwd-rate", action="store_true",
-                    help="skip the forward-only rate measured after the timed region (profiler runs: the trace then "
-                         "holds the timed step's kernels only)")
+                    help="with --full: skip the forward-only rate and the other step measurements after the timed region "
+                         "(profiler runs: the trace then holds the timed step's kernels only)")
     a = ap.parse_args()
     if a.batch is None:
         a.batch = 256 if a.mode == "train" else 64
@@ -167,8 +185,9 @@ def main():
             print("[bench] %s (t=%.1f s)" % (msg, time.perf_counter() - t_start), file=sys.stderr, flush=True)
 
     note("model built")
+    res = None   # the last step's outputs stay referenced through the next step, in the warm-up as in the timed loop
     for _ in range(a.warmup):
-        step()
+        res = step()
     sync_all()
     note("warm-up done")
     # HIP events around every step, on the stream the kernels are launched on (torch's current stream: the library is
@@ -178,7 +197,7 @@ def main():
     t0 = time.perf_counter()
     evs[0].record()
     for i in range(a.steps):
-        step()
+        res = step()
         evs[i + 1].record()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
@@ -192,13 +211,19 @@ def main():
     ms_per_step = elapsed / a.steps * 1e3
     value = world * a.batch * a.steps / elapsed
     note("timed region done: %.3f ms/step" % ms_per_step)
+    if a.dump_outputs and rank == 0:
+        # before anything below runs another step: these are the timed path's own results
+        arrays = step_outputs(res, full) if train else trunk_outputs(res)
+        total = write_outputs(a.dump_outputs, arrays)
+        note("outputs written to %s (%d arrays, %.1f MB)" % (a.dump_outputs, len(arrays), total / 1e6))
     f_enc = enc_flops_per_seq(S, cfg.hidden_size, cfg.num_hidden_layers, cfg.intermediate_size)
+    side = a.full   # everything from here to the result line is a side measurement: --full only
 
     # the same K steps with every padded row computed (the reference's own amount of work per step): reported beside
     # `value`, not part of the timed region above
     value_all_rows = None
     # (the condition must not depend on a rank's own batch: every rank runs the same number of collective steps)
-    if train and engine.compact_rows and a.batch * S >= engine.compact_min_rows and not a.no_fwd_rate:
+    if side and train and engine.compact_rows and a.batch * S >= engine.compact_min_rows and not a.no_fwd_rate:
         engine.compact_rows = False
         for _ in range(2):
             step()
@@ -219,7 +244,7 @@ def main():
 
     # forward-only rate in the same process (train mode): not part of the timed region above
     fwd_value = None
-    if train and not a.no_fwd_rate:
+    if side and train and not a.no_fwd_rate:
         for _ in range(3):
             fwd_step()
         sync_all()
@@ -238,7 +263,7 @@ def main():
     # BASELINE configs[1] under the same clock (train mode, one GPU): the trunk forward at B = 64 -- the number north_star's
     # 40 % target is quoted on -- with its HIP-vs-oracle differences; outside the timed region above
     fwd_b64, fwd_b64_out = None, None
-    if train and world == 1 and not a.no_fwd_rate:
+    if side and train and world == 1 and not a.no_fwd_rate:
         b64 = make_batch(cfg, 64, a.text, a.regions, seed=1234 + rank, device=dev, with_labels=False)
         was = trunk.training
         full.eval()
@@ -276,7 +301,7 @@ def main():
     # B = 36 (8 x 36 viewpoint candidates over 8 GPUs) -- the number that bounds the strong scaling of a 288-sequence job;
     # same engine and weights, 10 warm-up (tunes the B = 36 shapes) + 20 timed steps, outside the timed region above
     b36 = None
-    if train and world == 1 and not a.no_fwd_rate and a.batch != 36:
+    if side and train and world == 1 and not a.no_fwd_rate and a.batch != 36:
         bt36 = make_batch(cfg, 36, a.text, a.regions, seed=1234 + rank, device=dev, with_labels=True)
         for _ in range(10):
             engine.train_step(bt36)
@@ -312,7 +337,7 @@ def main():
     # N > 1: what the collective actually saw, so that a SCALE record proves itself -- backend, ranks, DISTINCT devices,
     # library version, bytes per step -- and the exposed communication: the same step with the gradient exchange left out
     collective = None
-    if dist is not None:
+    if side and dist is not None:
         pr = torch.cuda.get_device_properties(dev)
         ident = "%s|%s|%s:%s:%s" % (socket.gethostname(), getattr(pr, "uuid", None), getattr(pr, "pci_domain_id", None),
                                     getattr(pr, "pci_bus_id", None), getattr(pr, "pci_device_id", None))
@@ -350,12 +375,13 @@ def main():
             "env": {k: os.environ.get(k) for k in ("NCCL_MAX_NCHANNELS", "NCCL_MIN_NCHANNELS", "VT_GEMM_RESERVE_CUS", "VT_GRAD_COMM")},
         }
 
-    note("side measurements done")
+    if side:
+        note("side measurements done")
     # ---- live per-kernel timing (HIP events on the launch stream), outside the timed region ----
     roofline = None
     kernels = None
     hbm_step_bytes, traffic_src = None, None
-    if rank == 0 and not a.no_kernel_timing:
+    if side and rank == 0 and not a.no_kernel_timing:
         ops.profile_begin()
         for _ in range(3):
             if train:
@@ -405,9 +431,10 @@ def main():
     if train and engine.last_layout is not None:
         f_exec = 3 * enc_flops_rows(engine.last_layout.length.tolist(), cfg.hidden_size, cfg.num_hidden_layers,
                                     cfg.intermediate_size)
-    note("kernel timing done")
+    if side:
+        note("kernel timing done")
     cpu_baseline = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if side and rank == 0 and world == 1 and not a.no_cpu_baseline:
         gpu_out = fwd_b64_out
         if not train:   # the first two sequences of the timed batch: HIP outputs for the logits diff against the oracle
             with torch.no_grad():
@@ -529,6 +556,78 @@ def hip_outputs_for_diff(full, trunk, batch):
     return dict(batch={k: v.cpu() for k, v in sub.items()}, state={k: v.detach().cpu() for k, v in full.state_dict().items()},
                 sequence_output=seq_sub.float().cpu().view(B2, S2, -1), prediction_scores=sc.float().cpu().view(B2, S2, -1),
                 action_scores=act.float().cpu(), sequence_output_in_full_batch=seq_full.float().cpu())
+
+
+DUMP_MAX_ELEMS = 15 << 20         # float32 elements over all dumped arrays (62.9 MB): larger outputs are sampled to fit
+DUMP_PARAM_SAMPLE = 4096          # elements per parameter (and its gradient) in params_sample / grads_sample
+DUMP_MAX_BYTES = 64 * 10 ** 6
+STEP_OUTPUT_NAMES = ("loss", "mask_loss", "next_loss", "token_loss", "words_acc", "action_acc", "token_acc")
+
+
+def fixed_sample(t, k, seed):
+    """`t` flattened; when it holds more than k elements, k of them at indices drawn from a generator seeded with `seed`
+    (depends on numel, k and seed only: the same positions in every run and build)."""
+    import torch
+
+    flat = t.detach().reshape(-1)
+    if flat.numel() <= k:
+        return flat
+    g = torch.Generator(device="cpu")
+    g.manual_seed(int(seed))
+    idx = torch.randint(0, flat.numel(), (k,), generator=g)
+    return flat[idx.to(flat.device)]
+
+
+def fit_outputs(tensors):
+    """{name: tensor} -> {name: float32 ndarray} within DUMP_MAX_ELEMS in all: every array whole when they fit, else the
+    smaller ones whole and each larger one a fixed sample (fixed_sample, seeded by its position) of an equal share of
+    what is left."""
+    names = list(tensors)
+    left, out = DUMP_MAX_ELEMS, {}
+    by_size = sorted(names, key=lambda n: tensors[n].numel())
+    for i, n in enumerate(by_size):
+        t = tensors[n].detach()
+        k = min(t.numel(), left // (len(by_size) - i))
+        out[n] = (t if k == t.numel() else fixed_sample(t, k, names.index(n))).float().cpu().numpy()
+        left -= k
+    return {n: out[n] for n in names}
+
+
+def step_outputs(res, model):
+    """Train mode: the 7-tuple train_step returned, and a fixed sample of every parameter and of its gradient after the
+    step (model.named_parameters() order, DUMP_PARAM_SAMPLE elements each)."""
+    import torch
+
+    tensors = {n: torch.as_tensor(v) for n, v in zip(STEP_OUTPUT_NAMES, res)}
+    ps, gs = [], []
+    for i, (_, p) in enumerate(model.named_parameters()):
+        ps.append(fixed_sample(p, DUMP_PARAM_SAMPLE, i).float())
+        g = p.grad if p.grad is not None else torch.zeros_like(p)
+        gs.append(fixed_sample(g, DUMP_PARAM_SAMPLE, i).float())
+    tensors["params_sample"], tensors["grads_sample"] = torch.cat(ps), torch.cat(gs)
+    return fit_outputs(tensors)
+
+
+def trunk_outputs(res):
+    """Fwd mode: what the trunk's forward returned, (sequence_output, pooled_output), whole while they fit the budget."""
+    return fit_outputs({(("sequence_output", "pooled_output")[i] if i < 2 else "output_%d" % i): t for i, t in enumerate(res)})
+
+
+def write_outputs(out_dir, arrays):
+    """arrays {name: ndarray} -> out_dir/<name>.npy as float32 (float64 kept); returns the bytes written."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    prepared = {}
+    for name, arr in arrays.items():
+        arr = np.asarray(arr)
+        prepared[name] = arr if arr.dtype == np.float64 else arr.astype(np.float32)
+    total = sum(arr.nbytes for arr in prepared.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError("outputs of %d bytes exceed the %d-byte limit of --dump-outputs" % (total, DUMP_MAX_BYTES))
+    for name, arr in prepared.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return total
 
 
 def device_info(dev):

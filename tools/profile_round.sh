@@ -17,7 +17,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 export VT_TUNE_FILE="$PWD/$OUT/tune_$NAME.json"
 rm -f "$VT_TUNE_FILE"
-python3 bench.py --no-cpu-baseline --steps 10 --warmup 3 "${ARGS[@]}" > "$OUT/bench_${NAME}_live.json" 2> "$OUT/${NAME}_live.err"
+python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 3 "${ARGS[@]}" > "$OUT/bench_${NAME}_live.json" 2> "$OUT/${NAME}_live.err"
 echo "$NAME live done" >> "$OUT/progress.txt"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_$NAME" -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-fwd-rate --no-kernel-timing "${ARGS[@]}" > "$OUT/${NAME}_trace.out" 2> "$OUT/${NAME}_trace.err"
 echo "$NAME trace done" >> "$OUT/progress.txt"

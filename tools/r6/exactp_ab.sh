@@ -3,7 +3,7 @@
 O=gpurun_out/exactp_ab; mkdir -p $O
 for i in 1 2; do
   for bits in 8 16; do
-    VT_ATTN_DROPOUT_BITS=$bits python bench.py --no-cpu-baseline --no-fwd-rate --steps 20 --warmup 8 > $O/b256_${bits}_$i.json 2> $O/b256_${bits}_$i.err
+    VT_ATTN_DROPOUT_BITS=$bits python bench.py --full --no-cpu-baseline --no-fwd-rate --steps 20 --warmup 8 > $O/b256_${bits}_$i.json 2> $O/b256_${bits}_$i.err
     echo "b256 bits=$bits run $i done" >> $O/progress.txt
   done
 done

@@ -3,7 +3,7 @@
 O=gpurun_out/reverse_ab; mkdir -p $O
 for rep in 1 2 3; do
   for k in 0 3072 2304 768; do
-    VT_GEMM_REVERSE_K=$k python bench.py --no-cpu-baseline --no-fwd-rate --steps 20 --warmup 8 > $O/b256_k${k}_$rep.json 2> $O/b256_k${k}_$rep.err
+    VT_GEMM_REVERSE_K=$k python bench.py --full --no-cpu-baseline --no-fwd-rate --steps 20 --warmup 8 > $O/b256_k${k}_$rep.json 2> $O/b256_k${k}_$rep.err
     echo "k=$k rep=$rep" >> $O/progress.txt
   done
 done

@@ -13,7 +13,7 @@ cp gpurun_out/prof_$R/*_pmc_hbm_traffic.json gpurun_out/prof_$R/*_pmc_hbm_traffi
 # kernel-trace summary of the B = 36 step (configs[3]'s per-GPU share): gpurun_out/prof_$R/b36_kernel_stats.csv
 bash tools/trace_step.sh prof_$R b36 --batch 36 > $O/trace_b36.log 2>&1 && echo "trace b36 done" >> $O/progress.txt
 cp gpurun_out/prof_$R/b36_kernel_stats.csv profiles/$R/ 2>/dev/null
-b() { name=$1; shift; python bench.py "$@" --no-cpu-baseline > $O/bench_$name.json 2> $O/bench_$name.err; echo $name >> $O/progress.txt; }
+b() { name=$1; shift; python bench.py "$@" --full --no-cpu-baseline > $O/bench_$name.json 2> $O/bench_$name.err; echo $name >> $O/progress.txt; }
 b b36 --batch 36 --steps 50 --warmup 10
 # configs[3]'s per-GPU share under each multi-rank GEMM policy, on one rank (the kernel mix an 8-GPU run executes)
 VT_FORCE_MULTI_RANK_GEMM=1 b b36_policy_stood_down --batch 36 --steps 50 --warmup 10
@@ -27,7 +27,7 @@ b shipped_s767_b8 --text 511 --regions 256 --batch 8 --steps 30 --warmup 8
 b shipped_s767_b8_fwd --mode fwd --text 511 --regions 256 --batch 8 --steps 50 --warmup 10
 b text511_b8_fwd --mode fwd --text 511 --regions 0 --batch 8 --steps 50 --warmup 10
 b 2rank --gpus 2 --share-gpu --backend gloo --batch 36 --steps 20 --warmup 5
-python bench.py --mode fwd > $O/bench_fwd_b64.json 2> $O/bench_fwd_b64.err; echo fwdb64 >> $O/progress.txt
-python bench.py > $O/bench_train_b256.json 2> $O/bench_train_b256.err; echo train >> $O/progress.txt
+python bench.py --full --mode fwd > $O/bench_fwd_b64.json 2> $O/bench_fwd_b64.err; echo fwdb64 >> $O/progress.txt
+python bench.py --full > $O/bench_train_b256.json 2> $O/bench_train_b256.err; echo train >> $O/progress.txt
 cp $O/bench_*.json profiles/$R/ 2>/dev/null
 tail -3 $O/progress.txt

@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 export VT_TUNE_FILE="$PWD/$OUT/tune_$NAME.json"
 rm -f "$VT_TUNE_FILE"
-python3 bench.py --no-cpu-baseline --steps 30 --warmup 5 --no-fwd-rate "$@" > "$OUT/bench_${NAME}_live.json" 2> "$OUT/${NAME}_live.err"
+python3 bench.py --full --no-cpu-baseline --steps 30 --warmup 5 --no-fwd-rate "$@" > "$OUT/bench_${NAME}_live.json" 2> "$OUT/${NAME}_live.err"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_$NAME" -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-fwd-rate --no-kernel-timing "$@" > "$OUT/${NAME}_trace.out" 2> "$OUT/${NAME}_trace.err"
 S=$(find "$OUT/trace_$NAME" -name "*kernel_stats.csv" | head -1)
 cp "$S" "$OUT/${NAME}_kernel_stats.csv"
