@@ -512,6 +512,73 @@ int vt_embed_layernorm_f32(const int64_t* input_ids, const int64_t* token_type_i
                            float* out, int64_t ld_out, int B, int T, int S, int H, int n_word, int n_pos, int n_type,
                            float eps, int* err_flag, vt_stream_t stream);
 
+/* ---- fp32 training step (ABI 13) -----------------------------------------------------------------------------------
+ * PretrainEngine(model, precision="fp32"): the reference's training arithmetic (tasks/viewpoint_select/pretrain.py:191 back-
+ * propagates fp32; no AMP).  Every operand, activation, gradient and accumulator is fp32, products on v_mfma_f32_32x32x2_f32;
+ * no float atomics (every reduction has a fixed order: a step is bitwise reproducible).  Dropout: the keep decisions of the
+ * bf16 kernels on the padded layout (site seeds and element indices as there; drop_p / drop_seed / drop_site as everywhere).
+ *
+ * vt_gemm_f32_ex: vt_linear_f32 / vt_bmm_f32 with the training forms.  a_is_km: A is given as [K, M] (element (m, k) at
+ *   a[k * lda + m]), so dW = dY^T . X and the attention's dK = dS^T . Q, dV = P^T . dC come from the same kernel.  pre_act
+ *   (optional, C's layout): alpha * a . op(w) + bias before the activation.  drop_*: dropout of act(...) BEFORE the residual
+ *   add (LN(dropout(dense(x)) + input)), element index = row * N + col with the row before the grp remap.  accumulate: C +=.
+ *   split: the K range in `split` parts (0: vt_gemm_f32_split_count's choice; 1: none), partial planes in split_ws
+ *   (split * M * N floats), summed in split order; split > 1 takes no bias / residual / act / pre_act / dropout / remap and
+ *   batch * heads == 1. */
+int vt_gemm_f32_ex(const float* a, int64_t lda, int64_t a_stride_b, int64_t a_stride_h, int a_is_km, const float* w,
+                   int64_t ldw, int64_t w_stride_b, int64_t w_stride_h, int w_is_kn, const float* bias, const float* residual,
+                   int64_t ldr, float* out, int64_t ldc, int64_t c_stride_b, int64_t c_stride_h, float* pre_act, int M, int N,
+                   int K, int act, float alpha, int batch, int heads, int grp_rows, int grp_stride, int accumulate, int split,
+                   float* split_ws, float drop_p, uint64_t drop_seed, uint32_t drop_site, vt_stream_t stream);
+/* The K-split count vt_gemm_f32_ex takes for split = 0: a function of the shape only (1 .. 16). */
+int vt_gemm_f32_split_count(int M, int N, int K);
+/* out[c] (+)= sum over rows of x[r, c] (bias gradients) in a fixed order; ws: ceil(rows / 256) * cols floats. */
+int vt_colsum_f32(const float* x, int64_t ldx, int64_t rows, int cols, float* out, int accumulate, float* ws,
+                  vt_stream_t stream);
+/* BertLayerNorm backward from the saved input x [M, H] and dL/dy g (g row of row r: (r / grp_rows) * grp_stride + r % grp_rows;
+ * grp_rows 0: r).  p_in > 0: g is first multiplied by the keep mask / (1 - p_in) of site_in (element r * H + c: the embedding
+ * and image sites, whose dropout follows the LayerNorm).  dx (optional) = dL/dx; dx_drop (optional) = dx * keep / (1 - p_out) of
+ * site_out (the gradient of a dropped dense output).  dgamma / dbeta (+)= their sums in a fixed order.  ws:
+ * vt_layernorm_bwd_f32_ws_floats(M, H) floats.  H % 4 == 0, H <= 1024. */
+int64_t vt_layernorm_bwd_f32_ws_floats(int64_t M, int H);
+int vt_layernorm_bwd_f32(const float* x, int64_t ldx, const float* g, int64_t ldg, int grp_rows, int grp_stride,
+                         const float* gamma, float eps, float* dx, int64_t lddx, float* dx_drop, int64_t ldd, float* dgamma,
+                         float* dbeta, int accumulate, float* ws, int64_t M, int H, float p_in, uint32_t site_in, float p_out,
+                         uint32_t site_out, uint64_t drop_seed, vt_stream_t stream);
+/* vt_layernorm_rows (fp32 in and out; x rows compact, y rows remapped) followed by the dropout of a site, element index
+ * row * H + col (row before the remap):
+ * the embeddings' and the image rows' LayerNorm + dropout (encoder.py:267-270, :280-284). */
+int vt_layernorm_drop_f32(const float* x, int64_t ldx, float* y, int64_t ldy, const float* gamma, const float* beta, int64_t M,
+                          int H, float eps, int grp_rows, int grp_stride, float drop_p, uint64_t drop_seed, uint32_t drop_site,
+                          vt_stream_t stream);
+/* Attention probabilities of a training step on the scores [B * nh * S, S] (row pitch ld), row (b * nh + h) * S + q.
+ * backward 0: probs = softmax(probs * scale + mask) in place (mask_mode -1 none, 0 raw [B, S] -> (1 - m) * -10000, 2 additive
+ * [B, S, S]); probs_dropped = probs * keep / (1 - p) * head_scale[h] (head_scale [nh] or NULL).  backward 1: probs holds the
+ * forward's probs, probs_dropped dL/d(probs_dropped) on entry and dL/d(scores before scale) on return:
+ * P (g - rowsum(g P)) * scale, g = dPd * keep / (1 - p) * head_scale.  keep: the attention site's decision (vt_keep_attn's
+ * stream for head b * nh + h, element q * pitch + k, pitch = S rounded up to a multiple of 4). */
+int vt_attn_softmax_train_f32(int backward, float* probs, float* probs_dropped, int64_t ld, int B, int nh, int S, float scale,
+                              const float* mask, int mask_mode, const float* head_scale, float drop_p, uint64_t drop_seed,
+                              uint32_t drop_site, vt_stream_t stream);
+/* out = g * GELU'(pre) (erf form), n fp32 elements. */
+int vt_dgelu_f32(const float* g, const float* pre, float* out, int64_t n, vt_stream_t stream);
+/* out [B * T, H] = word[id] + position[pos id] + token_type[type id] (BertEmbeddings' sum before its LayerNorm); ids as in
+ * vt_embed_layernorm (err_flag set on an out-of-range id). */
+int vt_embed_sum_f32(const int64_t* input_ids, const int64_t* token_type_ids, const int64_t* position_ids, const float* word,
+                     const float* pos, const float* type, float* out, int B, int T, int H, int n_word, int n_pos, int n_type,
+                     int* err_flag, vt_stream_t stream);
+/* y[r, c] = x[remap(r), c] * keep / (1 - p), element index r * cols + c (x row of r: (r / grp_rows) * grp_stride + r % grp_rows). */
+int vt_dropout_rows_f32(const float* x, int64_t ldx, int grp_rows, int grp_stride, float* y, int64_t ldy, int64_t rows, int cols,
+                        float drop_p, uint64_t drop_seed, uint32_t drop_site, vt_stream_t stream);
+/* vt_ce_softmax_rows / vt_ce_double_softmax_rows / vt_action_head_f32 with fp32 gradient rows (dz [rows, Vpad], lddz % 8 == 0,
+ * 16-byte aligned; the action head's dlogits [B, Ap]). */
+int vt_ce_softmax_rows_g32(const float* z, int64_t ldz, const int64_t* y, float* loss_row, int64_t* amax, float* dz, int64_t lddz,
+                           int64_t rows, int V, int Vpad, float scale, vt_stream_t stream);
+int vt_ce_double_softmax_rows_g32(const float* z, int64_t ldz, const int64_t* y, float* loss_row, int64_t* amax, float* dz,
+                                  int64_t lddz, int64_t rows, int V, int Vpad, float scale, vt_stream_t stream);
+int vt_action_head_g32(const float* logits, int64_t ld, const int64_t* next_action, int B, int A, float grad_scale, float* dlogits,
+                       int64_t ldd, int Ap, float* loss_acc, vt_stream_t stream);
+
 /* ---- pretrain input preparation on the device ---------------------------------------------------
  * PretrainDataset._mask_tokens (tasks/viewpoint_select/data_loader_pretrain.py:549-613) over n = B*T tokens: BERT's
  * 15 % / 80-10-10 rule with the random draws handed in (u_* uniform [0,1) fp32, random_words int64), forced masking of

@@ -193,6 +193,31 @@ SIGNATURES = {
     "vt_embed_layernorm_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
                                        c_void_p, c_void_p]),
+    "vt_gemm_f32_ex": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p,
+                               c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int,
+                               c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_float, c_uint64, c_uint32,
+                               c_void_p]),
+    "vt_gemm_f32_split_count": (c_int, [c_int, c_int, c_int]),
+    "vt_colsum_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "vt_layernorm_bwd_f32_ws_floats": (c_int64, [c_int64, c_int]),
+    "vt_layernorm_bwd_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_float, c_void_p, c_int64,
+                                     c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_float, c_uint32,
+                                     c_float, c_uint32, c_uint64, c_void_p]),
+    "vt_layernorm_drop_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_float, c_int,
+                                      c_int, c_float, c_uint64, c_uint32, c_void_p]),
+    "vt_attn_softmax_train_f32": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_void_p, c_int,
+                                          c_void_p, c_float, c_uint64, c_uint32, c_void_p]),
+    "vt_dgelu_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "vt_embed_sum_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                 c_int, c_int, c_int, c_void_p, c_void_p]),
+    "vt_dropout_rows_f32": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_float, c_uint64,
+                                    c_uint32, c_void_p]),
+    "vt_ce_softmax_rows_g32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int,
+                                       c_float, c_void_p]),
+    "vt_ce_double_softmax_rows_g32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int,
+                                              c_int, c_float, c_void_p]),
+    "vt_action_head_g32": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_float, c_void_p, c_int64, c_int, c_void_p,
+                                   c_void_p]),
     "vt_linear_ln_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_float,
                                   c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_int,
                                   c_int, c_void_p]),

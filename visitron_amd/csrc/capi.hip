@@ -58,6 +58,36 @@ struct BatchRowsArgs {
 int vt_batch_rows_dispatch(const BatchRowsArgs& a, int lists, hipStream_t stream);
 int vt_action_head_dispatch(const float* z, long ldz, const long* y, int B, int A, float grad_scale, void* dz, long lddz, int Ap,
                             float* out, hipStream_t stream);
+// fp32 training step (fp32_path.hip, fp32_train.hip, rowops.hip)
+int vt_action_head_dispatch2(const float* z, long ldz, const long* y, int B, int A, float grad_scale, void* dz, long lddz, int Ap,
+                             float* out, int dz_f32, hipStream_t stream);
+int vt_ce_softmax_dispatch2(const float* z, long ldz, const int64_t* y, float* loss_row, int64_t* amax, void* dz, long lddz,
+                            long rows, int V, int Vpad, float scale, int dz_f32, hipStream_t stream);
+int vt_ce_double_softmax_dispatch2(const float* z, long ldz, const int64_t* y, float* loss_row, int64_t* amax, void* dz, long lddz,
+                                   long rows, int V, int Vpad, float scale, int dz_f32, hipStream_t stream);
+int vt_gemm_f32_split_for(int M, int N, int K);
+int vt_gemm_f32_ex_dispatch(const float* A, long lda, long sA_b, long sA_h, int a_is_km, const float* W, long ldw, long sW_b,
+                            long sW_h, int w_is_kn, const float* bias, const float* R, long ldr, float* C, long ldc, long sC_b,
+                            long sC_h, float* pre, int M, int N, int K, int act, float alpha, int batch, int heads,
+                            int grp_rows, int grp_stride, int accumulate, int split, float* ws, DropCfg drop,
+                            hipStream_t stream);
+int vt_layernorm_f32_drop_dispatch(const void* x, long ldx, int x_is_f32, void* y, long ldy, int y_is_f32, const float* gamma,
+                                   const float* beta, long M, int H, float eps, int grp_rows, int grp_stride, DropCfg drop,
+                                   hipStream_t stream, int drop_entry);
+int vt_colsum_f32_dispatch(const float* x, long ldx, long rows, int cols, float* out, int accumulate, float* ws,
+                           hipStream_t stream);
+int vt_ln_bwd_f32_blocks(long M);
+int vt_ln_bwd_f32_dispatch(const float* x, long ldx, const float* g, long ldg, int grp_rows, int grp_stride, const float* gamma,
+                           float* dx, long lddx, float* dx_drop, long ldd, float* partial, long M, int H, float eps, DropCfg din,
+                           DropCfg dout, hipStream_t stream);
+int vt_attn_softmax_f32_dispatch(int backward, float* x, float* pd, long ld, int B, int nh, int S, float scale, const float* mask,
+                                 int mask_mode, const float* head_scale, DropCfg drop, hipStream_t stream);
+int vt_dgelu_f32_dispatch(const float* g, const float* pre, float* out, long n, hipStream_t stream);
+int vt_embed_sum_f32_dispatch(const int64_t* ids, const int64_t* type_ids, const int64_t* pos_ids, const float* word,
+                              const float* pos, const float* type, float* e, int B, int T, int H, int n_word, int n_pos,
+                              int n_type, int* err, hipStream_t stream);
+int vt_dropout_rows_f32_dispatch(const float* x, long ldx, int grp_rows, int grp_stride, float* y, long ldy, long rows, int cols,
+                                 DropCfg d, hipStream_t stream);
 int vt_gemm_splitk_dispatch(const void* A, long lda, const void* W, long ldw, void* C, long ldc, float* ws, int M, int N, int K,
                             int ksplit, hipStream_t stream);
 int vt_attention_probs_dispatch(const void* qkv, long ld_qkv, const float* mask, int mask_additive, const float* head_scale,
@@ -141,7 +171,7 @@ const char* vt_error_string(int code) {
   }
 }
 
-int vt_abi_version(void) { return 12; }
+int vt_abi_version(void) { return 13; }
 
 // attention-probability dropout: 16-bit fields (default since ABI 12: p in steps of 1/65536, two keys per hash word -- the
 // reference's nn.Dropout(0.1) runs as 0.100006) or 8-bit fields (rounds 4-5's form: steps of 1/256, four keys per hash word,
@@ -621,6 +651,99 @@ int vt_embed_layernorm_f32(const int64_t* input_ids, const int64_t* token_type_i
                            float eps, int* err_flag, vt_stream_t stream) {
   return vt_embed_layernorm_f32_dispatch(input_ids, token_type_ids, position_ids, word, pos, type, gamma, beta, out, ld_out,
                                          B, T, S, H, n_word, n_pos, n_type, eps, err_flag, (hipStream_t)stream);
+}
+
+// ---- fp32 training step (ABI 13) ---------------------------------------------------------------------------------
+int vt_gemm_f32_ex(const float* a, int64_t lda, int64_t a_stride_b, int64_t a_stride_h, int a_is_km, const float* w,
+                   int64_t ldw, int64_t w_stride_b, int64_t w_stride_h, int w_is_kn, const float* bias, const float* residual,
+                   int64_t ldr, float* out, int64_t ldc, int64_t c_stride_b, int64_t c_stride_h, float* pre_act, int M, int N,
+                   int K, int act, float alpha, int batch, int heads, int grp_rows, int grp_stride, int accumulate, int split,
+                   float* split_ws, float drop_p, uint64_t drop_seed, uint32_t drop_site, vt_stream_t stream) {
+  if (!(drop_p >= 0.f && drop_p < 1.f)) return VT_ERR_UNSUPPORTED;
+  return vt_gemm_f32_ex_dispatch(a, lda, a_stride_b, a_stride_h, a_is_km, w, ldw, w_stride_b, w_stride_h, w_is_kn, bias, residual,
+                                 ldr, out, ldc, c_stride_b, c_stride_h, pre_act, M, N, K, act, alpha, batch, heads, grp_rows,
+                                 grp_stride, accumulate, split, split_ws, vt_make_drop(drop_p, drop_seed, drop_site),
+                                 (hipStream_t)stream);
+}
+
+int vt_gemm_f32_split_count(int M, int N, int K) { return vt_gemm_f32_split_for(M, N, K); }
+
+int vt_colsum_f32(const float* x, int64_t ldx, int64_t rows, int cols, float* out, int accumulate, float* ws,
+                  vt_stream_t stream) {
+  return vt_colsum_f32_dispatch(x, ldx, rows, cols, out, accumulate, ws, (hipStream_t)stream);
+}
+
+int64_t vt_layernorm_bwd_f32_ws_floats(int64_t M, int H) {
+  const long nb = vt_ln_bwd_f32_blocks(M);
+  return nb * 2L * H + 2L * ((nb + 255) / 256) * H;
+}
+
+int vt_layernorm_bwd_f32(const float* x, int64_t ldx, const float* g, int64_t ldg, int grp_rows, int grp_stride,
+                         const float* gamma, float eps, float* dx, int64_t lddx, float* dx_drop, int64_t ldd, float* dgamma,
+                         float* dbeta, int accumulate, float* ws, int64_t M, int H, float p_in, uint32_t site_in, float p_out,
+                         uint32_t site_out, uint64_t drop_seed, vt_stream_t stream) {
+  if (!dgamma || !dbeta || !ws) return VT_ERR_NULL;
+  if (!(p_in >= 0.f && p_in < 1.f && p_out >= 0.f && p_out < 1.f)) return VT_ERR_UNSUPPORTED;
+  const long nb = vt_ln_bwd_f32_blocks(M);
+  float* partial = ws;
+  float* cws = ws + nb * 2L * H;
+  int rc = vt_ln_bwd_f32_dispatch(x, ldx, g, ldg, grp_rows, grp_stride, gamma, dx, lddx, dx_drop, ldd, partial, M, H, eps,
+                                  vt_make_drop(p_in, drop_seed, site_in), vt_make_drop(p_out, drop_seed, site_out),
+                                  (hipStream_t)stream);
+  if (rc == VT_OK) rc = vt_colsum_f32_dispatch(partial, 2L * H, nb, H, dgamma, accumulate, cws, (hipStream_t)stream);
+  if (rc == VT_OK) rc = vt_colsum_f32_dispatch(partial + H, 2L * H, nb, H, dbeta, accumulate, cws + ((nb + 255) / 256) * H,
+                                               (hipStream_t)stream);
+  return rc;
+}
+
+int vt_layernorm_drop_f32(const float* x, int64_t ldx, float* y, int64_t ldy, const float* gamma, const float* beta, int64_t M,
+                          int H, float eps, int grp_rows, int grp_stride, float drop_p, uint64_t drop_seed, uint32_t drop_site,
+                          vt_stream_t stream) {
+  if (!(drop_p >= 0.f && drop_p < 1.f)) return VT_ERR_UNSUPPORTED;
+  return vt_layernorm_f32_drop_dispatch(x, ldx, 1, y, ldy, 1, gamma, beta, M, H, eps, grp_rows, grp_stride,
+                                        vt_make_drop(drop_p, drop_seed, drop_site), (hipStream_t)stream, 1);
+}
+
+int vt_attn_softmax_train_f32(int backward, float* probs, float* probs_dropped, int64_t ld, int B, int nh, int S, float scale,
+                              const float* mask, int mask_mode, const float* head_scale, float drop_p, uint64_t drop_seed,
+                              uint32_t drop_site, vt_stream_t stream) {
+  if (!vt_attn_drop_ok(drop_p, attn_drop_bits())) return VT_ERR_UNSUPPORTED;
+  return vt_attn_softmax_f32_dispatch(backward, probs, probs_dropped, ld, B, nh, S, scale, mask, mask_mode, head_scale,
+                                      vt_make_drop_attn(drop_p, drop_seed, drop_site, attn_drop_bits()), (hipStream_t)stream);
+}
+
+int vt_dgelu_f32(const float* g, const float* pre, float* out, int64_t n, vt_stream_t stream) {
+  return vt_dgelu_f32_dispatch(g, pre, out, n, (hipStream_t)stream);
+}
+
+int vt_embed_sum_f32(const int64_t* input_ids, const int64_t* token_type_ids, const int64_t* position_ids, const float* word,
+                     const float* pos, const float* type, float* out, int B, int T, int H, int n_word, int n_pos, int n_type,
+                     int* err_flag, vt_stream_t stream) {
+  return vt_embed_sum_f32_dispatch(input_ids, token_type_ids, position_ids, word, pos, type, out, B, T, H, n_word, n_pos, n_type,
+                                   err_flag, (hipStream_t)stream);
+}
+
+int vt_dropout_rows_f32(const float* x, int64_t ldx, int grp_rows, int grp_stride, float* y, int64_t ldy, int64_t rows, int cols,
+                        float drop_p, uint64_t drop_seed, uint32_t drop_site, vt_stream_t stream) {
+  if (!(drop_p >= 0.f && drop_p < 1.f)) return VT_ERR_UNSUPPORTED;
+  return vt_dropout_rows_f32_dispatch(x, ldx, grp_rows, grp_stride, y, ldy, rows, cols, vt_make_drop(drop_p, drop_seed, drop_site),
+                                      (hipStream_t)stream);
+}
+
+int vt_ce_softmax_rows_g32(const float* z, int64_t ldz, const int64_t* y, float* loss_row, int64_t* amax, float* dz, int64_t lddz,
+                           int64_t rows, int V, int Vpad, float scale, vt_stream_t stream) {
+  return vt_ce_softmax_dispatch2(z, ldz, y, loss_row, amax, dz, lddz, rows, V, Vpad, scale, 1, (hipStream_t)stream);
+}
+
+int vt_ce_double_softmax_rows_g32(const float* z, int64_t ldz, const int64_t* y, float* loss_row, int64_t* amax, float* dz,
+                                  int64_t lddz, int64_t rows, int V, int Vpad, float scale, vt_stream_t stream) {
+  return vt_ce_double_softmax_dispatch2(z, ldz, y, loss_row, amax, dz, lddz, rows, V, Vpad, scale, 1, (hipStream_t)stream);
+}
+
+int vt_action_head_g32(const float* logits, int64_t ld, const int64_t* next_action, int B, int A, float grad_scale, float* dlogits,
+                       int64_t ldd, int Ap, float* loss_acc, vt_stream_t stream) {
+  return vt_action_head_dispatch2(logits, ld, (const long*)next_action, B, A, grad_scale, dlogits, ldd, Ap, loss_acc, 1,
+                                  (hipStream_t)stream);
 }
 
 }  // extern "C"

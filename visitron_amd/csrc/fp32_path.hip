@@ -13,6 +13,11 @@
 //                       head's nn.Softmax (encoder.py:323-326)
 //   layernorm_rows_f32  BertLayerNorm, fp32 or bf16 rows in, fp32 or bf16 rows out
 //   embed_layernorm_f32 BertEmbeddings (encoder.py:267-269) with fp32 output
+//
+// Training (PretrainEngine(..., precision="fp32"), fp32_train.hip) reuses gemm_f32_128 for every product of the step: the
+// A-transposed operand (a_is_km) gives the weight gradients dW = dY^T . X and the attention's dK = dS^T . Q / dV = P^T . dC,
+// a fixed-order split of the K range (partial planes, summed in order by gemm_f32_split_reduce) keeps a long token-row
+// reduction on the whole chip, and the epilogue can save the pre-activation, apply a dropout site and accumulate into C.
 #include "common.hpp"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
@@ -29,6 +34,13 @@ struct GemmF32Args {
   int grp_rows, grp_stride;   // output row remap as in the bf16 GEMM (0: identity)
   int vec_a, vec_w; // 16-byte loads allowed (aligned base, stride and K / N multiples of 4)
   float alpha;
+  // training forms (fp32_train.hip; all zero / null in the inference entry points)
+  int a_is_km;      // 0: A is [M, K]; 1: A is [K, M] (element (m, k) at A[k * lda + m]: dY^T of a weight gradient)
+  int accumulate;   // C += result (C's old value is added after the residual)
+  int split, kchunk;  // blockIdx.z = (b * heads + h) * split + s; split s covers K range [s * kchunk, (s + 1) * kchunk)
+  float* ws;        // split > 1: partial plane s at ws + s * M * N (row-major [M, N], alpha applied, nothing else)
+  float* pre;       // saved alpha * acc + bias before the activation (same layout as C), or null
+  DropCfg drop;     // dropout of act(...) before the residual add, element index = row * N + col (row before the remap)
 };
 
 #define GF_BM 128
@@ -48,7 +60,9 @@ __global__ __launch_bounds__(256) void gemm_f32_128(GemmF32Args g) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int m0 = blockIdx.y * GF_BM, n0 = blockIdx.x * GF_BN;
-  const int zb = blockIdx.z / g.heads, zh = blockIdx.z - zb * g.heads;
+  const int zs = blockIdx.z % g.split, zbh = blockIdx.z / g.split;
+  const int zb = zbh / g.heads, zh = zbh - zb * g.heads;
+  const int kbeg = zs * g.kchunk, kend = min(g.K, kbeg + g.kchunk);
   const float* A = g.A + zb * g.sA_b + zh * g.sA_h;
   const float* W = g.W + zb * g.sW_b + zh * g.sW_h;
   float* C = g.C + zb * g.sC_b + zh * g.sC_h;
@@ -69,35 +83,47 @@ __global__ __launch_bounds__(256) void gemm_f32_128(GemmF32Args g) {
     for (int p = 0; p < 2; ++p) {
       const int row = row0 + ld_row + 64 * p;
       const int k = k0 + ld_kq;
-      if (row < nrows && vec && k + 3 < g.K) {
+      if (row < nrows && vec && k + 3 < kend) {
         const f32x4 v = *(const f32x4*)(base + (long)row * ld + k);
         r[p][0] = v[0]; r[p][1] = v[1]; r[p][2] = v[2]; r[p][3] = v[3];
       } else {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) r[p][i] = (row < nrows && k + i < g.K) ? base[(long)row * ld + k + i] : 0.f;
+        for (int i = 0; i < 4; ++i) r[p][i] = (row < nrows && k + i < kend) ? base[(long)row * ld + k + i] : 0.f;
       }
     }
   };
   // W given as [K, N]: a thread owns two (k, n-quad) pieces: k = tid/32 (+8), n = (tid%32)*4
-  auto load_kn = [&](int k0, float (&r)[2][4]) {
+  // an operand given as [K, cols] (W with w_is_kn, A with a_is_km): a thread owns two (k, col-quad) pieces: k = tid/32 (+8),
+  // col = (tid%32)*4
+  auto load_kx = [&](const float* base, long ld, int c0, int ncols, bool vec, int k0, float (&r)[2][4]) {
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
       const int k = k0 + (tid >> 5) + 8 * p;
-      const int n = n0 + (tid & 31) * 4;
-      if (k < g.K && g.vec_w && n + 3 < g.N) {
-        const f32x4 v = *(const f32x4*)(W + (long)k * g.ldw + n);
+      const int n = c0 + (tid & 31) * 4;
+      if (k < kend && vec && n + 3 < ncols) {
+        const f32x4 v = *(const f32x4*)(base + (long)k * ld + n);
         r[p][0] = v[0]; r[p][1] = v[1]; r[p][2] = v[2]; r[p][3] = v[3];
       } else {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) r[p][i] = (k < g.K && n + i < g.N) ? W[(long)k * g.ldw + n + i] : 0.f;
+        for (int i = 0; i < 4; ++i) r[p][i] = (k < kend && n + i < ncols) ? base[(long)k * ld + n + i] : 0.f;
       }
     }
   };
+  auto load_kn = [&](int k0, float (&r)[2][4]) { load_kx(W, g.ldw, n0, g.N, g.vec_w != 0, k0, r); };
+  auto load_a = [&](int k0) {
+    if (g.a_is_km) load_kx(A, g.lda, m0, g.M, g.vec_a != 0, k0, ra);
+    else load_rowmajor(A, g.lda, m0, g.M, k0, g.vec_a != 0, ra);
+  };
   auto store_tile = [&](int buf) {
+    if (g.a_is_km) {
 #pragma unroll
-    for (int p = 0; p < 2; ++p)
+      for (int p = 0; p < 2; ++p) *(f32x4*)&As[buf][(tid >> 5) + 8 * p][(tid & 31) * 4] = (f32x4){ra[p][0], ra[p][1], ra[p][2], ra[p][3]};
+    } else {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) As[buf][ld_kq + i][ld_row + 64 * p] = ra[p][i];
+      for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) As[buf][ld_kq + i][ld_row + 64 * p] = ra[p][i];
+    }
     if (g.w_is_kn) {
 #pragma unroll
       for (int p = 0; p < 2; ++p) *(f32x4*)&Bs[buf][(tid >> 5) + 8 * p][(tid & 31) * 4] = (f32x4){rb[p][0], rb[p][1], rb[p][2], rb[p][3]};
@@ -109,17 +135,18 @@ __global__ __launch_bounds__(256) void gemm_f32_128(GemmF32Args g) {
     }
   };
 
-  const int nk = (g.K + GF_BK - 1) / GF_BK;
-  load_rowmajor(A, g.lda, m0, g.M, 0, g.vec_a != 0, ra);
-  if (g.w_is_kn) load_kn(0, rb); else load_rowmajor(W, g.ldw, n0, g.N, 0, g.vec_w != 0, rb);
+  const int nk = (kend - kbeg + GF_BK - 1) / GF_BK;
+  load_a(kbeg);
+  if (g.w_is_kn) load_kn(kbeg, rb); else load_rowmajor(W, g.ldw, n0, g.N, kbeg, g.vec_w != 0, rb);
   store_tile(0);
   __syncthreads();
   const int fr = lane & 31, fk = lane >> 5;
   for (int kt = 0; kt < nk; ++kt) {
     const int buf = kt & 1;
     if (kt + 1 < nk) {
-      load_rowmajor(A, g.lda, m0, g.M, (kt + 1) * GF_BK, g.vec_a != 0, ra);
-      if (g.w_is_kn) load_kn((kt + 1) * GF_BK, rb); else load_rowmajor(W, g.ldw, n0, g.N, (kt + 1) * GF_BK, g.vec_w != 0, rb);
+      const int kn = kbeg + (kt + 1) * GF_BK;
+      load_a(kn);
+      if (g.w_is_kn) load_kn(kn, rb); else load_rowmajor(W, g.ldw, n0, g.N, kn, g.vec_w != 0, rb);
     }
 #pragma unroll
     for (int kk = 0; kk < GF_BK; kk += 2) {
@@ -146,9 +173,17 @@ __global__ __launch_bounds__(256) void gemm_f32_128(GemmF32Args g) {
       for (int v = 0; v < 16; ++v) {
         const int row = m0 + wm * 64 + 32 * i + 8 * (v >> 2) + 4 * fk + (v & 3);
         if (row >= g.M) continue;
-        float x = gf_act(acc[i][j][v] * g.alpha + bv, g.act);
-        if (g.R) x += g.R[(long)row * g.ldr + col];
+        if (g.split > 1) {   // a partial plane: summed in split order by gemm_f32_split_reduce
+          g.ws[((long)zs * g.M + row) * g.N + col] = acc[i][j][v] * g.alpha;
+          continue;
+        }
+        const float pv = acc[i][j][v] * g.alpha + bv;
         const long orow = g.grp_rows ? (long)(row / g.grp_rows) * g.grp_stride + (row % g.grp_rows) : (long)row;
+        if (g.pre) g.pre[orow * g.ldc + col] = pv;
+        float x = gf_act(pv, g.act);
+        if (g.drop.thresh) x = vt_keep(g.drop, (uint32_t)((long)row * g.N + col)) ? x * g.drop.scale : 0.f;
+        if (g.R) x += g.R[(long)row * g.ldr + col];
+        if (g.accumulate) x += C[orow * g.ldc + col];
         C[orow * g.ldc + col] = x;
       }
     }
@@ -167,12 +202,72 @@ int vt_gemm_f32_dispatch(const float* A, long lda, long sA_b, long sA_h, const f
   g.bias = bias; g.R = R; g.ldr = ldr; g.C = C; g.ldc = ldc; g.sC_b = sC_b; g.sC_h = sC_h;
   g.M = M; g.N = N; g.K = K; g.act = act; g.w_is_kn = w_is_kn; g.heads = heads; g.grp_rows = grp_rows; g.grp_stride = grp_stride;
   g.alpha = alpha;
+  g.a_is_km = 0; g.accumulate = 0; g.split = 1; g.kchunk = (K + GF_BK - 1) / GF_BK * GF_BK; g.ws = nullptr; g.pre = nullptr;
+  g.drop.thresh = 0; g.drop.seed = 0; g.drop.scale = 1.0f;
   auto ok4 = [](const void* p, long ld, long s0, long s1) { return (((uintptr_t)p & 15) == 0) && (ld % 4 == 0) && (s0 % 4 == 0) && (s1 % 4 == 0); };
   g.vec_a = ok4(A, lda, sA_b, sA_h) ? 1 : 0;
   g.vec_w = ok4(W, ldw, sW_b, sW_h) ? 1 : 0;
   const dim3 grid((N + GF_BN - 1) / GF_BN, (M + GF_BM - 1) / GF_BM, batch * heads);
   if (grid.y > 65535) return VT_ERR_BAD_SHAPE;
   hipLaunchKernelGGL(gemm_f32_128, grid, dim3(256), 0, stream, g);
+  return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
+}
+
+// C (+)= sum_s ws[s] in split order (the weight gradients' K split): bitwise the same result for the same shape and split.
+__global__ __launch_bounds__(256) void gemm_f32_split_reduce(const float* __restrict__ ws, int split, int M, int N,
+                                                             float* __restrict__ C, long ldc, int accumulate) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)M * N) return;
+  const long row = i / N, col = i - row * N;
+  float s = accumulate ? C[row * ldc + col] : 0.f;
+  float t = ws[i];
+  for (int k = 1; k < split; ++k) t += ws[(long)k * M * N + i];
+  C[row * ldc + col] = s + t;
+}
+
+// How many K ranges a product of this shape is split into (a function of the shape only): enough workgroups to cover the
+// 256 CUs about twice when the [M, N] tiles alone cannot, each range at least 512 deep, at most 16 ranges.
+int vt_gemm_f32_split_for(int M, int N, int K) {
+  const long tiles = (long)((M + GF_BM - 1) / GF_BM) * ((N + GF_BN - 1) / GF_BN);
+  int s = (int)(512 / tiles);
+  s = s < K / 512 ? s : K / 512;
+  return s < 1 ? 1 : (s > 16 ? 16 : s);
+}
+
+int vt_gemm_f32_ex_dispatch(const float* A, long lda, long sA_b, long sA_h, int a_is_km, const float* W, long ldw, long sW_b,
+                            long sW_h, int w_is_kn, const float* bias, const float* R, long ldr, float* C, long ldc, long sC_b,
+                            long sC_h, float* pre, int M, int N, int K, int act, float alpha, int batch, int heads,
+                            int grp_rows, int grp_stride, int accumulate, int split, float* ws, DropCfg drop,
+                            hipStream_t stream) {
+  if (!A || !W || !C) return VT_ERR_NULL;
+  if (M <= 0 || N <= 0 || K <= 0 || batch <= 0 || heads <= 0) return VT_ERR_BAD_SHAPE;
+  if (act != 0 && act != 1 && act != 2) return VT_ERR_UNSUPPORTED;
+  if (grp_rows < 0 || (grp_rows > 0 && grp_stride < grp_rows)) return VT_ERR_BAD_SHAPE;
+  if (split <= 0) split = vt_gemm_f32_split_for(M, N, K);
+  if (split > 1) {
+    // partial planes carry alpha * A . op(W) only: the rest of the epilogue has no place in a K split
+    if (!ws) return VT_ERR_NULL;
+    if (batch * heads != 1 || bias || R || pre || act || grp_rows || drop.thresh) return VT_ERR_UNSUPPORTED;
+  }
+  if ((long)batch * heads * split > 65535) return VT_ERR_BAD_SHAPE;
+  GemmF32Args g;
+  g.A = A; g.lda = lda; g.sA_b = sA_b; g.sA_h = sA_h; g.W = W; g.ldw = ldw; g.sW_b = sW_b; g.sW_h = sW_h;
+  g.bias = bias; g.R = R; g.ldr = ldr; g.C = C; g.ldc = ldc; g.sC_b = sC_b; g.sC_h = sC_h;
+  g.M = M; g.N = N; g.K = K; g.act = act; g.w_is_kn = w_is_kn; g.heads = heads; g.grp_rows = grp_rows; g.grp_stride = grp_stride;
+  g.alpha = alpha;
+  g.a_is_km = a_is_km ? 1 : 0; g.accumulate = accumulate ? 1 : 0; g.split = split; g.ws = ws; g.pre = pre; g.drop = drop;
+  g.kchunk = ((K + split - 1) / split + GF_BK - 1) / GF_BK * GF_BK;
+  auto ok4 = [](const void* p, long ld, long s0, long s1) { return (((uintptr_t)p & 15) == 0) && (ld % 4 == 0) && (s0 % 4 == 0) && (s1 % 4 == 0); };
+  g.vec_a = ok4(A, lda, sA_b, sA_h) ? 1 : 0;
+  g.vec_w = ok4(W, ldw, sW_b, sW_h) ? 1 : 0;
+  const dim3 grid((N + GF_BN - 1) / GF_BN, (M + GF_BM - 1) / GF_BM, batch * heads * split);
+  if (grid.y > 65535) return VT_ERR_BAD_SHAPE;
+  hipLaunchKernelGGL(gemm_f32_128, grid, dim3(256), 0, stream, g);
+  if (split > 1) {
+    const long n = (long)M * N;
+    hipLaunchKernelGGL(gemm_f32_split_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ws, split, M, N, C, ldc,
+                       g.accumulate);
+  }
   return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
 }
 
@@ -237,6 +332,8 @@ struct LnF32Args {
   const float* gamma; const float* beta;
   long M; int H; float eps;
   int grp_rows, grp_stride;
+  DropCfg drop;   // fp32 output only: dropout after the LayerNorm, element index = row * H + col (row before the remap)
+  int x_compact;  // 1: x rows are not remapped (x [M, H] compact, only y rows are); 0: both (in place)
 };
 
 template <bool IN_F32, bool OUT_F32>
@@ -255,11 +352,11 @@ __global__ __launch_bounds__(256) void layernorm_rows_f32(LnF32Args a) {
     for (int i = 0; i < 4; ++i) v[c][i] = 0.f;
     if (col < a.H) {
       if (IN_F32) {
-        const f32x4 t = *(const f32x4*)((const float*)a.x + prow * a.ldx + col);
+        const f32x4 t = *(const f32x4*)((const float*)a.x + (a.x_compact ? row : prow) * a.ldx + col);
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[c][i] = t[i];
       } else {
-        const uint2 t = *(const uint2*)((const bf16_t*)a.x + prow * a.ldx + col);
+        const uint2 t = *(const uint2*)((const bf16_t*)a.x + (a.x_compact ? row : prow) * a.ldx + col);
         v[c][0] = bf16lo(t.x); v[c][1] = bf16hi(t.x); v[c][2] = bf16lo(t.y); v[c][3] = bf16hi(t.y);
       }
 #pragma unroll
@@ -285,6 +382,10 @@ __global__ __launch_bounds__(256) void layernorm_rows_f32(LnF32Args a) {
       float o[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) o[i] = (v[c][i] - u) * rstd * g4[i] + b4[i];
+      if (OUT_F32 && a.drop.thresh) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = vt_keep(a.drop, (uint32_t)(row * a.H + col + i)) ? o[i] * a.drop.scale : 0.f;
+      }
       if (OUT_F32) {
         *(f32x4*)((float*)a.y + prow * a.ldy + col) = (f32x4){o[0], o[1], o[2], o[3]};
       } else {
@@ -296,15 +397,30 @@ __global__ __launch_bounds__(256) void layernorm_rows_f32(LnF32Args a) {
   }
 }
 
+int vt_layernorm_f32_drop_dispatch(const void* x, long ldx, int x_is_f32, void* y, long ldy, int y_is_f32, const float* gamma,
+                                   const float* beta, long M, int H, float eps, int grp_rows, int grp_stride, DropCfg drop,
+                                   hipStream_t stream, int drop_entry = 1);
+
 int vt_layernorm_f32_dispatch(const void* x, long ldx, int x_is_f32, void* y, long ldy, int y_is_f32, const float* gamma,
                               const float* beta, long M, int H, float eps, int grp_rows, int grp_stride, hipStream_t stream) {
+  DropCfg none;
+  none.thresh = 0; none.seed = 0; none.scale = 1.0f;
+  return vt_layernorm_f32_drop_dispatch(x, ldx, x_is_f32, y, ldy, y_is_f32, gamma, beta, M, H, eps, grp_rows, grp_stride, none,
+                                        stream, 0);
+}
+
+// drop_entry (vt_layernorm_drop_f32): x rows compact, y rows remapped; 0 (vt_layernorm_rows): both remapped (in place)
+int vt_layernorm_f32_drop_dispatch(const void* x, long ldx, int x_is_f32, void* y, long ldy, int y_is_f32, const float* gamma,
+                                   const float* beta, long M, int H, float eps, int grp_rows, int grp_stride, DropCfg drop,
+                                   hipStream_t stream, int drop_entry) {
+  if (drop.thresh && !y_is_f32) return VT_ERR_UNSUPPORTED;
   if (!x || !y || !gamma || !beta) return VT_ERR_NULL;
   if (M <= 0 || H <= 0 || (H % 4) || H > 4096) return VT_ERR_BAD_SHAPE;
   const int ax = x_is_f32 ? 15 : 7, ay = y_is_f32 ? 15 : 7;
   if ((ldx % 4) || (ldy % 4) || ((uintptr_t)x & ax) || ((uintptr_t)y & ay) || (((uintptr_t)gamma | (uintptr_t)beta) & 15)) return VT_ERR_BAD_ALIGN;
   LnF32Args a;
   a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy; a.gamma = gamma; a.beta = beta; a.M = M; a.H = H; a.eps = eps;
-  a.grp_rows = grp_rows; a.grp_stride = grp_stride;
+  a.grp_rows = grp_rows; a.grp_stride = grp_stride; a.drop = drop; a.x_compact = drop_entry;
   const dim3 grid((unsigned)((M + 3) / 4)), block(256);
   if (x_is_f32 && y_is_f32) hipLaunchKernelGGL((layernorm_rows_f32<true, true>), grid, block, 0, stream, a);
   else if (x_is_f32) hipLaunchKernelGGL((layernorm_rows_f32<true, false>), grid, block, 0, stream, a);

@@ -1253,15 +1253,39 @@ int vt_transpose_batch_dispatch(const void* const* in, const long* ldi, void* co
   return VT_OK;
 }
 
+// gradient rows of the loss kernels: bf16 (the bf16 engine) or fp32 (the fp32 training step), N consecutive values
+template <int N>
+__device__ __forceinline__ void ce_store(bf16_t* p, const float* g) {
+  if (N == 8) {
+    u32x4 o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = pack_bf16x2(g[2 * i], g[2 * i + 1]);
+    *(u32x4*)p = o;
+  } else {
+    u32x2 o;
+    o[0] = pack_bf16x2(g[0], g[1]);
+    o[1] = pack_bf16x2(g[2], g[3]);
+    *(u32x2*)p = o;
+  }
+}
+template <int N>
+__device__ __forceinline__ void ce_store(float* p, const float* g) {
+#pragma unroll
+  for (int i = 0; i < N; i += 4) *(f32x4*)(p + i) = (f32x4){g[i], g[i + 1], g[i + 2], g[i + 3]};
+}
+__device__ __forceinline__ void ce_store1(bf16_t* p, float v) { *p = f32_to_bf16(v); }
+__device__ __forceinline__ void ce_store1(float* p, float v) { *p = v; }
+
 // ---------------------------------------------------------------------------------------------
 // Fused softmax cross-entropy over the MLM logits (tasks/viewpoint_select/encoder.py:387-389 + the
 // argmax of :399 + the backward of the criterion): per supervised row, ONE kernel produces
 //   loss_row = logsumexp(z) - z[y],  argmax(z),  dz = (softmax(z) - onehot(y)) * scale   (bf16, zero-padded)
 // instead of torch's log_softmax / exp / scatter / mul / cast passes over a [rows, 30522] fp32 tensor.
 // One 256-thread workgroup per row; the row (<= 122 KB) is read twice (second pass from L2).
+template <typename DZ>
 __global__ __launch_bounds__(256) void ce_softmax_rows(const float* __restrict__ z, long ldz, const int64_t* __restrict__ y,
                                                        float* __restrict__ loss_row, int64_t* __restrict__ amax,
-                                                       bf16_t* __restrict__ dz, long lddz, int V, int Vpad, float scale) {
+                                                       DZ* __restrict__ dz, long lddz, int V, int Vpad, float scale) {
   __shared__ float red_m[4], red_s[4], red_bv[4];
   __shared__ int red_bi[4];
   const long row = blockIdx.x;
@@ -1316,7 +1340,7 @@ __global__ __launch_bounds__(256) void ce_softmax_rows(const float* __restrict__
   }
   // pass 2: gradient row (skipped when the caller wants the loss and the argmax only: dz == nullptr)
   if (!dz) return;
-  bf16_t* dp = dz + row * lddz;
+  DZ* dp = dz + row * lddz;
   for (int c = tid * 8; c < Vpad; c += 2048) {
     float g[8];
 #pragma unroll
@@ -1330,10 +1354,7 @@ __global__ __launch_bounds__(256) void ce_softmax_rows(const float* __restrict__
       }
       g[i] = p;
     }
-    u32x4 o;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = pack_bf16x2(g[2 * i], g[2 * i + 1]);
-    *(u32x4*)(dp + c) = o;
+    ce_store<8>(dp + c, g);
   }
 }
 
@@ -1342,10 +1363,10 @@ __global__ __launch_bounds__(256) void ce_softmax_rows(const float* __restrict__
 // gradient is that value times scale / sum (no second exponential, no second read).  Against the two-pass kernel above
 // (one exponential pair per element in the online pass, a third in the gradient pass, the row read twice): 440 -> ~170 us
 // for [4 272, 30 522] at B = 256.
-template <int NV>
+template <int NV, typename DZ>
 __global__ __launch_bounds__(256) void ce_softmax_rows_reg(const float* __restrict__ z, long ldz, const int64_t* __restrict__ y,
                                                            float* __restrict__ loss_row, int64_t* __restrict__ amax,
-                                                           bf16_t* __restrict__ dz, long lddz, int V, int Vpad, float scale) {
+                                                           DZ* __restrict__ dz, long lddz, int V, int Vpad, float scale) {
   __shared__ float red_a[4], red_b[4];
   __shared__ int red_i[4];
   const long row = blockIdx.x;
@@ -1398,7 +1419,7 @@ __global__ __launch_bounds__(256) void ce_softmax_rows_reg(const float* __restri
     amax[row] = bi;
   }
   if (!dz) return;
-  bf16_t* dp = dz + row * lddz;
+  DZ* dp = dz + row * lddz;
   const float f = scale / s;
 #pragma unroll
   for (int k = 0; k < NV; ++k) {
@@ -1407,31 +1428,41 @@ __global__ __launch_bounds__(256) void ce_softmax_rows_reg(const float* __restri
       float g[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) g[i] = (c + i < V) ? v[k][i] * f - ((c + i == (int)label) ? scale : 0.f) : 0.f;
-      u32x2 o;
-      o[0] = pack_bf16x2(g[0], g[1]);
-      o[1] = pack_bf16x2(g[2], g[3]);
-      *(u32x2*)(dp + c) = o;
+      ce_store<4>(dp + c, g);
     }
   }
 }
 
-int vt_ce_softmax_dispatch(const float* z, long ldz, const int64_t* y, float* loss_row, int64_t* amax, void* dz, long lddz,
-                           long rows, int V, int Vpad, float scale, hipStream_t stream) {
-  if (!z || !y || !loss_row || !amax) return VT_ERR_NULL;
-  if (!dz) { Vpad = (V + 7) / 8 * 8; lddz = Vpad; }   // no gradient row wanted
-  if (rows <= 0 || V <= 0 || Vpad < V || (Vpad % 8) || lddz < Vpad) return VT_ERR_BAD_SHAPE;
-  if ((ldz % 4) || (lddz % 8) || (((uintptr_t)z | (uintptr_t)dz) & 15)) return VT_ERR_BAD_ALIGN;
+template <typename DZ>
+static void ce_softmax_launch(const float* z, long ldz, const int64_t* y, float* loss_row, int64_t* amax, DZ* dz, long lddz,
+                              long rows, int V, int Vpad, float scale, hipStream_t stream) {
   const int need = (Vpad + 1023) / 1024;   // f32x4 per thread
   if (need <= 8)
-    hipLaunchKernelGGL(ce_softmax_rows_reg<8>, dim3((unsigned)rows), dim3(256), 0, stream, z, ldz, y, loss_row, amax, (bf16_t*)dz,
+    hipLaunchKernelGGL((ce_softmax_rows_reg<8, DZ>), dim3((unsigned)rows), dim3(256), 0, stream, z, ldz, y, loss_row, amax, dz,
                        lddz, V, Vpad, scale);
   else if (need <= 32)
-    hipLaunchKernelGGL(ce_softmax_rows_reg<32>, dim3((unsigned)rows), dim3(256), 0, stream, z, ldz, y, loss_row, amax, (bf16_t*)dz,
+    hipLaunchKernelGGL((ce_softmax_rows_reg<32, DZ>), dim3((unsigned)rows), dim3(256), 0, stream, z, ldz, y, loss_row, amax, dz,
                        lddz, V, Vpad, scale);
   else
-    hipLaunchKernelGGL(ce_softmax_rows, dim3((unsigned)rows), dim3(256), 0, stream, z, ldz, y, loss_row, amax, (bf16_t*)dz, lddz,
+    hipLaunchKernelGGL((ce_softmax_rows<DZ>), dim3((unsigned)rows), dim3(256), 0, stream, z, ldz, y, loss_row, amax, dz, lddz,
                        V, Vpad, scale);
+}
+
+// dz_f32: the gradient rows are fp32 (the fp32 training step) instead of bf16
+int vt_ce_softmax_dispatch2(const float* z, long ldz, const int64_t* y, float* loss_row, int64_t* amax, void* dz, long lddz,
+                            long rows, int V, int Vpad, float scale, int dz_f32, hipStream_t stream) {
+  if (!z || !y || !loss_row || !amax) return VT_ERR_NULL;
+  if (!dz) { Vpad = (V + 7) / 8 * 8; lddz = Vpad; dz_f32 = 0; }   // no gradient row wanted
+  if (rows <= 0 || V <= 0 || Vpad < V || (Vpad % 8) || lddz < Vpad) return VT_ERR_BAD_SHAPE;
+  if ((ldz % 4) || (lddz % 8) || (((uintptr_t)z | (uintptr_t)dz) & 15)) return VT_ERR_BAD_ALIGN;
+  if (dz_f32) ce_softmax_launch(z, ldz, y, loss_row, amax, (float*)dz, lddz, rows, V, Vpad, scale, stream);
+  else ce_softmax_launch(z, ldz, y, loss_row, amax, (bf16_t*)dz, lddz, rows, V, Vpad, scale, stream);
   return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
+}
+
+int vt_ce_softmax_dispatch(const float* z, long ldz, const int64_t* y, float* loss_row, int64_t* amax, void* dz, long lddz,
+                           long rows, int V, int Vpad, float scale, hipStream_t stream) {
+  return vt_ce_softmax_dispatch2(z, ldz, y, loss_row, amax, dz, lddz, rows, V, Vpad, scale, 0, stream);
 }
 
 // The masked-region-token head's loss (tasks/viewpoint_select/encoder.py:323-326, 380-385): token_head = Linear +
@@ -1447,9 +1478,10 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
   return red[0] + red[1] + red[2] + red[3];
 }
 
+template <typename DZ>
 __global__ __launch_bounds__(256) void ce_double_softmax_rows(const float* __restrict__ z, long ldz, const int64_t* __restrict__ y,
                                                               float* __restrict__ loss_row, int64_t* __restrict__ amax,
-                                                              bf16_t* __restrict__ dz, long lddz, int V, int Vpad, float scale) {
+                                                              DZ* __restrict__ dz, long lddz, int V, int Vpad, float scale) {
   __shared__ float red[4];
   __shared__ float red_bv[4];
   __shared__ int red_bi[4];
@@ -1513,7 +1545,7 @@ __global__ __launch_bounds__(256) void ce_double_softmax_rows(const float* __res
   }
   const float dot = t / s2 - py;   // sum_i (softmax(p)_i - onehot_i) p_i
   if (!dz) return;                 // loss and argmax only
-  bf16_t* dp = dz + row * lddz;
+  DZ* dp = dz + row * lddz;
   if (c0 < Vpad) {
     float gz[8];
 #pragma unroll
@@ -1521,23 +1553,29 @@ __global__ __launch_bounds__(256) void ce_double_softmax_rows(const float* __res
       const float dpi = e[i] / s2 - ((c0 + i == label) ? 1.0f : 0.f);
       gz[i] = (c0 + i < V) ? v[i] * (dpi - dot) * scale : 0.f;
     }
-    u32x4 o;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = pack_bf16x2(gz[2 * i], gz[2 * i + 1]);
-    *(u32x4*)(dp + c0) = o;
+    ce_store<8>(dp + c0, gz);
   }
+}
+
+int vt_ce_double_softmax_dispatch2(const float* z, long ldz, const int64_t* y, float* loss_row, int64_t* amax, void* dz, long lddz,
+                                   long rows, int V, int Vpad, float scale, int dz_f32, hipStream_t stream) {
+  if (!z || !y || !loss_row || !amax) return VT_ERR_NULL;
+  if (!dz) { Vpad = (V + 7) / 8 * 8; lddz = Vpad; dz_f32 = 0; }   // no gradient row wanted
+  if (rows <= 0 || V <= 0 || Vpad < V || (Vpad % 8) || lddz < Vpad) return VT_ERR_BAD_SHAPE;
+  if (Vpad > 2048) return VT_ERR_UNSUPPORTED;   // the row is held in registers: 256 threads x 8 classes
+  if ((lddz % 8) || ((uintptr_t)dz & 15)) return VT_ERR_BAD_ALIGN;
+  if (dz_f32)
+    hipLaunchKernelGGL(ce_double_softmax_rows<float>, dim3((unsigned)rows), dim3(256), 0, stream, z, ldz, y, loss_row, amax,
+                       (float*)dz, lddz, V, Vpad, scale);
+  else
+    hipLaunchKernelGGL(ce_double_softmax_rows<bf16_t>, dim3((unsigned)rows), dim3(256), 0, stream, z, ldz, y, loss_row, amax,
+                       (bf16_t*)dz, lddz, V, Vpad, scale);
+  return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
 }
 
 int vt_ce_double_softmax_dispatch(const float* z, long ldz, const int64_t* y, float* loss_row, int64_t* amax, void* dz, long lddz,
                                   long rows, int V, int Vpad, float scale, hipStream_t stream) {
-  if (!z || !y || !loss_row || !amax) return VT_ERR_NULL;
-  if (!dz) { Vpad = (V + 7) / 8 * 8; lddz = Vpad; }   // no gradient row wanted
-  if (rows <= 0 || V <= 0 || Vpad < V || (Vpad % 8) || lddz < Vpad) return VT_ERR_BAD_SHAPE;
-  if (Vpad > 2048) return VT_ERR_UNSUPPORTED;   // the row is held in registers: 256 threads x 8 classes
-  if ((lddz % 8) || ((uintptr_t)dz & 15)) return VT_ERR_BAD_ALIGN;
-  hipLaunchKernelGGL(ce_double_softmax_rows, dim3((unsigned)rows), dim3(256), 0, stream, z, ldz, y, loss_row, amax, (bf16_t*)dz,
-                     lddz, V, Vpad, scale);
-  return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
+  return vt_ce_double_softmax_dispatch2(z, ldz, y, loss_row, amax, dz, lddz, rows, V, Vpad, scale, 0, stream);
 }
 
 // x *= dropout mask * scale in place (bf16 [rows, cols], element index = row * cols + col): masks the
@@ -1885,8 +1923,9 @@ int vt_batch_rows_dispatch(const BatchRowsArgs& a, int lists, hipStream_t stream
 //   dz = g - exp(l) * rowsum(g),  g = (exp(m) - onehot(y)) * valid * grad_scale / n_valid
 // (torch: two log_softmax, gather, clamp, exp, scatter_add, several multiplies and reductions = ~20 launches on a [256, 36]
 // tensor).  One workgroup, one wave per row in turn; A <= 64.  n_valid = 0 gives the NaN torch gives.
+template <typename DZ>
 __global__ __launch_bounds__(1024) void action_head_rows(const float* __restrict__ z, long ldz, const long* __restrict__ y, int B,
-                                                         int A, float grad_scale, bf16_t* __restrict__ dz, long lddz, int Ap,
+                                                         int A, float grad_scale, DZ* __restrict__ dz, long lddz, int Ap,
                                                          float* __restrict__ out /* loss, accuracy */) {
   __shared__ float red[16][2];
   __shared__ int redn[16];
@@ -1925,7 +1964,7 @@ __global__ __launch_bounds__(1024) void action_head_rows(const float* __restrict
     const float g = lane < A ? (__expf(m) - (lane == yc ? 1.f : 0.f)) * ((valid ? 1.f : 0.f) * (grad_scale * inv_n)) : 0.f;
     const float gs = wave_sum(g);
     const float d = g - __expf(l) * gs;
-    if (lane < Ap) dz[b * lddz + lane] = f32_to_bf16(lane < A ? d : 0.f);
+    if (lane < Ap) ce_store1(dz + b * lddz + lane, lane < A ? d : 0.f);
   }
   if (lane == 0) { red[wave][0] = loss; red[wave][1] = hits; }
   __syncthreads();
@@ -1937,12 +1976,22 @@ __global__ __launch_bounds__(1024) void action_head_rows(const float* __restrict
   }
 }
 
-int vt_action_head_dispatch(const float* z, long ldz, const long* y, int B, int A, float grad_scale, void* dz, long lddz, int Ap,
-                            float* out, hipStream_t stream) {
+int vt_action_head_dispatch2(const float* z, long ldz, const long* y, int B, int A, float grad_scale, void* dz, long lddz, int Ap,
+                             float* out, int dz_f32, hipStream_t stream) {
   if (!z || !y || !dz || !out) return VT_ERR_NULL;
   if (B <= 0 || A <= 0 || A > 64 || Ap < A || Ap > 64 || ldz < A || lddz < Ap) return VT_ERR_BAD_SHAPE;
-  hipLaunchKernelGGL(action_head_rows, dim3(1), dim3(1024), 0, stream, z, ldz, y, B, A, grad_scale, (bf16_t*)dz, lddz, Ap, out);
+  if (dz_f32)
+    hipLaunchKernelGGL(action_head_rows<float>, dim3(1), dim3(1024), 0, stream, z, ldz, y, B, A, grad_scale, (float*)dz, lddz, Ap,
+                       out);
+  else
+    hipLaunchKernelGGL(action_head_rows<bf16_t>, dim3(1), dim3(1024), 0, stream, z, ldz, y, B, A, grad_scale, (bf16_t*)dz, lddz,
+                       Ap, out);
   return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
+}
+
+int vt_action_head_dispatch(const float* z, long ldz, const long* y, int B, int A, float grad_scale, void* dz, long lddz, int Ap,
+                            float* out, hipStream_t stream) {
+  return vt_action_head_dispatch2(z, ldz, y, B, A, grad_scale, dz, lddz, Ap, out, 0, stream);
 }
 
 // ---- weight prefetch (round 6) --------------------------------------------------------------------------------------------------

@@ -1562,3 +1562,168 @@ def embed_layernorm_f32(ids, type_ids, pos_ids, word, pos, typ, gamma, beta, eps
                                             word.shape[0], pos.shape[0], typ.shape[0], float(eps), _ptr(err_flag), _stream())
     _lib.check(rc, "vt_embed_layernorm_f32")
     return out
+
+
+# ---- fp32 training step (PretrainEngine(..., precision="fp32"); visitron_amd/training_f32.py) ------------------------------
+def gemm_f32_ex(a, w, M, N, K, out, lda=None, ldw=None, ldc=None, a_is_km=False, w_is_kn=False, bias=None, residual=None,
+                ldr=None, pre_act=None, act=ACT_NONE, alpha=1.0, batch=1, heads=1, strides=((0, 0), (0, 0), (0, 0)),
+                grp_rows=0, grp_stride=0, accumulate=False, split=1, drop=NO_DROP):
+    """out (+)= act(alpha * op(a) . op(w) + bias) (+ residual) in fp32 (vt_gemm_f32_ex).  op(a): a [M,K], or [K,M] with
+    a_is_km (dY^T of a weight gradient); op(w): w [N,K], or [K,N] with w_is_kn.  strides: element strides ((a_b, a_h),
+    (w_b, w_h), (c_b, c_h)) of a (batch, head)-batched product.  split: the K range in parts (0: the library's choice for the
+    shape) summed in a fixed order.  pre_act: saved pre-activation (out's layout); drop: dropout before the residual add."""
+    _require_hip(a, w, out, bias, residual, pre_act)
+    _f32ok(a, w, out, bias, residual, pre_act)
+    lib = _lib.load()
+    if split == 0:
+        split = int(lib.vt_gemm_f32_split_count(M, N, K)) if batch * heads == 1 else 1
+    ws = torch.empty(split * M * N, dtype=torch.float32, device=a.device) if split > 1 else None
+    (sab, sah), (swb, swh), (scb, sch) = strides
+    with _timed("gemm_f32", 2.0 * M * N * K * batch * heads, 4.0 * (M * K + N * K + M * N) * batch * heads):
+        rc = lib.vt_gemm_f32_ex(_ptr(a), a.stride(0) if lda is None else lda, sab, sah, 1 if a_is_km else 0, _ptr(w),
+                                w.stride(0) if ldw is None else ldw, swb, swh, 1 if w_is_kn else 0, _ptr(bias), _ptr(residual),
+                                0 if residual is None else (residual.stride(0) if ldr is None else ldr), _ptr(out),
+                                out.stride(0) if ldc is None else ldc, scb, sch, _ptr(pre_act), M, N, K, int(act), float(alpha),
+                                batch, heads, grp_rows, grp_stride, 1 if accumulate else 0, int(split), _ptr(ws),
+                                float(drop[0]), int(drop[1]), int(drop[2]), _stream())
+    _lib.check(rc, "vt_gemm_f32_ex")
+    return out
+
+
+def colsum_f32(x, out, accumulate=False):
+    """out (+)= x.sum(0) over fp32 rows in a fixed order (bias gradients)."""
+    _require_hip(x, out)
+    _f32ok(x, out)
+    rows, cols = x.shape
+    ws = torch.empty(((rows + 255) // 256) * cols, dtype=torch.float32, device=x.device)
+    rc = _lib.load().vt_colsum_f32(_ptr(x), x.stride(0), rows, cols, _ptr(out), 1 if accumulate else 0, _ptr(ws), _stream())
+    _lib.check(rc, "vt_colsum_f32")
+    return out
+
+
+def wgrad_f32(dy, x, dw, db=None, accumulate=False, split=0):
+    """dw (+)= dy^T . x and db (+)= dy.sum(0): dy [rows, N], x [rows, K] fp32, dw [N, K] (K-split over the rows)."""
+    rows, N = dy.shape
+    K = x.shape[1]
+    gemm_f32_ex(dy, x, N, K, rows, dw, a_is_km=True, w_is_kn=True, accumulate=accumulate, split=split)
+    if db is not None:
+        colsum_f32(dy, db, accumulate=accumulate)
+
+
+def layernorm_bwd_f32(x, g, gamma, eps, dgamma, dbeta, dx=None, dx_drop=None, accumulate=False, M=None, grp_rows=0,
+                      grp_stride=0, drop_in=NO_DROP, drop_out=NO_DROP):
+    """BertLayerNorm backward in fp32 from its saved input x [M, H]: dx (+ dx * keep / (1 - p) of drop_out's site into
+    dx_drop), dgamma / dbeta (+)= their fixed-order sums.  g: dL/dy, row r at (r / grp_rows) * grp_stride + r % grp_rows;
+    drop_in: g is first masked by that site (the embedding / image dropout that follows their LayerNorm)."""
+    _require_hip(x, g, gamma, dx, dx_drop, dgamma, dbeta)
+    _f32ok(x, g, gamma, dx, dx_drop, dgamma, dbeta)
+    H = gamma.numel()
+    if M is None:
+        M = x.shape[0]
+    lib = _lib.load()
+    ws = torch.empty(int(lib.vt_layernorm_bwd_f32_ws_floats(M, H)), dtype=torch.float32, device=x.device)
+    assert drop_in[0] == 0 or drop_out[0] == 0 or drop_in[1] == drop_out[1]
+    seed = drop_in[1] if drop_in[0] > 0 else drop_out[1]
+    rc = lib.vt_layernorm_bwd_f32(_ptr(x), x.stride(0), _ptr(g), g.stride(0), grp_rows, grp_stride, _ptr(gamma), float(eps),
+                                  _ptr(dx), 0 if dx is None else dx.stride(0), _ptr(dx_drop),
+                                  0 if dx_drop is None else dx_drop.stride(0), _ptr(dgamma), _ptr(dbeta), 1 if accumulate else 0,
+                                  _ptr(ws), M, H, float(drop_in[0]), int(drop_in[2]), float(drop_out[0]), int(drop_out[2]),
+                                  int(seed), _stream())
+    _lib.check(rc, "vt_layernorm_bwd_f32")
+    return dx
+
+
+def layernorm_drop_f32(x, gamma, beta, eps, out, M=None, grp_rows=0, grp_stride=0, drop=NO_DROP):
+    """out[remap(r)] = dropout(LayerNorm(x[r])) in fp32, element index r * H + c."""
+    _require_hip(x, gamma, beta, out)
+    _f32ok(x, gamma, beta, out)
+    if M is None:
+        M = x.shape[0]
+    rc = _lib.load().vt_layernorm_drop_f32(_ptr(x), x.stride(0), _ptr(out), out.stride(0), _ptr(gamma), _ptr(beta), M,
+                                           gamma.numel(), float(eps), grp_rows, grp_stride, float(drop[0]), int(drop[1]),
+                                           int(drop[2]), _stream())
+    _lib.check(rc, "vt_layernorm_drop_f32")
+    return out
+
+
+def attn_softmax_train_f32(probs, probs_dropped, B, nh, S, mask=None, mask_mode=-1, head_scale=None, drop=NO_DROP,
+                           backward=False, scale=0.125):
+    """Forward: probs [B*nh*S, S] holds the scores; -> P (in place) and P * keep / (1 - p) * head_scale into probs_dropped.
+    Backward: probs_dropped holds dL/d(dropped probs) and becomes dL/d(scores) (the 1/8 included)."""
+    _require_hip(probs, probs_dropped, mask, head_scale)
+    _f32ok(probs, probs_dropped, mask, head_scale)
+    assert probs.stride(0) == probs_dropped.stride(0)
+    rc = _lib.load().vt_attn_softmax_train_f32(1 if backward else 0, _ptr(probs), _ptr(probs_dropped), probs.stride(0), B, nh, S,
+                                               float(scale), _ptr(mask), int(mask_mode) if mask is not None else -1,
+                                               _ptr(head_scale), float(drop[0]), int(drop[1]), int(drop[2]), _stream())
+    _lib.check(rc, "vt_attn_softmax_train_f32")
+    return probs_dropped
+
+
+def dgelu_f32(g, pre, out=None):
+    """out = g * GELU'(pre) (erf form), fp32, contiguous."""
+    _require_hip(g, pre, out)
+    assert g.is_contiguous() and pre.is_contiguous() and g.numel() == pre.numel()
+    if out is None:
+        out = torch.empty_like(g)
+    rc = _lib.load().vt_dgelu_f32(_ptr(g), _ptr(pre), _ptr(out), g.numel(), _stream())
+    _lib.check(rc, "vt_dgelu_f32")
+    return out
+
+
+def embed_sum_f32(ids, type_ids, pos_ids, word, pos, typ, out, err_flag=None):
+    """out [B*T, H] = word[ids] + pos[pos_ids or t] + typ[type_ids or 0] (BertEmbeddings' sum before its LayerNorm)."""
+    _require_hip(ids, word, out)
+    _f32ok(word, pos, typ, out)
+    B, T = ids.shape
+    rc = _lib.load().vt_embed_sum_f32(_ptr(ids), _ptr(type_ids), _ptr(pos_ids), _ptr(word), _ptr(pos), _ptr(typ), _ptr(out), B, T,
+                                      word.shape[1], word.shape[0], pos.shape[0], typ.shape[0], _ptr(err_flag), _stream())
+    _lib.check(rc, "vt_embed_sum_f32")
+    return out
+
+
+def dropout_rows_f32(x, out, rows, grp_rows=0, grp_stride=0, drop=NO_DROP):
+    """out[r] = x[remap(r)] * keep / (1 - p), element index r * cols + c."""
+    _require_hip(x, out)
+    _f32ok(x, out)
+    rc = _lib.load().vt_dropout_rows_f32(_ptr(x), x.stride(0), grp_rows, grp_stride, _ptr(out), out.stride(0), rows,
+                                         out.shape[1], float(drop[0]), int(drop[1]), int(drop[2]), _stream())
+    _lib.check(rc, "vt_dropout_rows_f32")
+    return out
+
+
+def ce_softmax_rows_g32(z, y, V, dz, scale):
+    """ce_softmax_rows with fp32 gradient rows dz [rows, Vpad]."""
+    _require_hip(z, y, dz)
+    rows = z.shape[0]
+    loss = torch.empty(rows, dtype=torch.float32, device=z.device)
+    amax = torch.empty(rows, dtype=torch.int64, device=z.device)
+    rc = _lib.load().vt_ce_softmax_rows_g32(_ptr(z), z.stride(0), _ptr(y), _ptr(loss), _ptr(amax), _ptr(dz), dz.stride(0), rows, V,
+                                            dz.shape[1], float(scale), _stream())
+    _lib.check(rc, "vt_ce_softmax_rows_g32")
+    return loss, amax
+
+
+def ce_double_softmax_rows_g32(z, y, V, dz, scale):
+    """ce_double_softmax_rows with fp32 gradient rows dz [rows, Vpad]."""
+    _require_hip(z, y, dz)
+    rows = z.shape[0]
+    loss = torch.empty(rows, dtype=torch.float32, device=z.device)
+    amax = torch.empty(rows, dtype=torch.int64, device=z.device)
+    rc = _lib.load().vt_ce_double_softmax_rows_g32(_ptr(z), z.stride(0), _ptr(y), _ptr(loss), _ptr(amax), _ptr(dz), dz.stride(0),
+                                                   rows, V, dz.shape[1], float(scale), _stream())
+    _lib.check(rc, "vt_ce_double_softmax_rows_g32")
+    return loss, amax
+
+
+def action_head_g32(logits, next_action, A, grad_scale, Ap):
+    """action_head with an fp32 gradient: -> (loss 0-d, accuracy 0-d, dlogits fp32 [B, Ap])."""
+    _require_hip(logits, next_action)
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and next_action.dtype == torch.int64
+    B = logits.shape[0]
+    dl = torch.empty((B, Ap), dtype=torch.float32, device=logits.device)
+    out = torch.empty(2, dtype=torch.float32, device=logits.device)
+    rc = _lib.load().vt_action_head_g32(_ptr(logits), logits.stride(0), _ptr(next_action.contiguous()), B, int(A),
+                                        float(grad_scale), _ptr(dl), Ap, int(Ap), _ptr(out), _stream())
+    _lib.check(rc, "vt_action_head_g32")
+    return out[0], out[1], dl

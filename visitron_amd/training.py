@@ -24,7 +24,7 @@ import os
 
 import torch.nn.functional as F
 
-from . import _lib, ops
+from . import _lib, ops, training_f32
 from .modeling import BertImgModelwithLocationEmbeds, PreTrainOscar, _i64, invalidate_packed_weights
 from .ops import ACT_MUL, ACT_GELU, ACT_NONE, ACT_TANH, BF16, round_up
 
@@ -198,7 +198,13 @@ class _State(object):
 class PretrainEngine(object):
     def __init__(self, model, lr=5e-5, weight_decay=0.05, eps=1e-8, betas=(0.9, 0.999), correct_bias=True,
                  schedule="linear", warmup_steps=0, t_total=20000, process_group=None, bucket_mb=64,
-                 loss_scale_by_world=True, attach_grads=True, grad_comm_dtype=None):
+                 loss_scale_by_world=True, attach_grads=True, grad_comm_dtype=None, precision="bf16"):
+        # precision: "bf16" (default: the bf16 kernels above) or "fp32" (the reference's training arithmetic: every operand,
+        # activation and gradient in fp32 on the fp32 matrix cores, visitron_amd.training_f32).  Independent of
+        # set_precision, which selects the inference arithmetic.
+        if precision not in ("bf16", "fp32"):
+            raise ValueError("precision must be 'bf16' or 'fp32', got %r" % (precision,))
+        self.precision = precision
         if isinstance(model, BertImgModelwithLocationEmbeds):
             model = _TrunkOnly(model)    # trunk-level training (the rollout's OscarEncoder owns just the trunk)
         assert isinstance(model, (PreTrainOscar, _TrunkOnly))
@@ -236,6 +242,8 @@ class PretrainEngine(object):
             raise ValueError("grad_comm_dtype must be 'bf16' or 'fp32'")
         self.grad_comm_dtype = grad_comm_dtype
         self.gemm_policy = "persistent GEMM on every CU (one rank, no collective beside it)"
+        if precision == "fp32" and self.world > 1:
+            raise NotImplementedError("PretrainEngine(precision='fp32') serves one rank")
         self.g16 = None
         if self.world > 1 and grad_comm_dtype == "bf16":
             self.g16 = torch.zeros(self.flat.total, dtype=BF16, device=self.flat.p.device)
@@ -270,7 +278,11 @@ class PretrainEngine(object):
         self.compact_min_rows = int(os.environ.get("VT_COMPACT_MIN_ROWS", "0"))
         self._side_stream = None
         self._fwd_serial = 0      # forwards issued: a backward must belong to the latest one (the buffers are shared)
-        self._build_tables()
+        if precision == "fp32":
+            self.overlap_adamw = False
+            training_f32.setup(self)
+        else:
+            self._build_tables()
 
     # ------------------------------------------------------------------------------ tables
     def _build_tables(self):
@@ -571,6 +583,10 @@ class PretrainEngine(object):
         (1 - m) * -10000 arithmetic) or the reference's 3-D form [B, S, S] (encoder.py:228-229); head_mask as the
         reference takes it (encoder.py:248-265; the layer loop then runs op by op: the head scaling sits between the
         attention kernel and the output projection in both directions).  backward=False: the forward and its 7-tuple only."""
+        if self.precision == "fp32":
+            if comm is not None:
+                raise NotImplementedError("PretrainEngine(precision='fp32') serves one rank")
+            return training_f32.forward_backward(self, batch, grad_scale, accumulate, head_mask, backward)
         st = self._trunk_fwd(batch, head_mask, batch["labels"], batch["token_labels"], self.model.training, True, comm)
         m, cfg, f, dev, emb, bufs = self.model, self.cfg, self.flat, st.dev, st.emb, st.bufs
         B, S, H, Mr, lay = st.B, st.S, st.H, st.Mr, st.lay
@@ -836,6 +852,12 @@ class PretrainEngine(object):
         compaction of forward_backward) and the other positions of sequence_output are zero."""
         if training is None:
             training = self.model.bert.training
+        if self.precision == "fp32":
+            if unmasked_only or want_hidden or want_attn:
+                raise NotImplementedError("PretrainEngine(precision='fp32') serves trunk_forward without unmasked_only, "
+                                          "want_hidden and want_attn")
+            st = training_f32.trunk_forward(self, batch, head_mask, bool(training))
+            return st.seq.view(st.B, st.S, st.H).clone(), st.pooled.clone(), st
         st = self._trunk_fwd(batch, head_mask, None, None, bool(training), bool(unmasked_only))
         # the caller's hidden states come from the fp16 copy of the last LayerNorm's output where the layer keeps one (the
         # bf16 copy is the heads' / pooler's GEMM operand)
@@ -899,6 +921,10 @@ class PretrainEngine(object):
         """Gradients of the trunk's parameters into the flat slab, given dL/d(sequence_output) [B,S,H] and / or
         dL/d(pooled_output) [B,H] (either may be None).  The pooler's gradients are zeroed when d_pooled is None, the
         region projection's when the forward had no regions."""
+        if self.precision == "fp32":
+            if d_hidden is not None:
+                raise NotImplementedError("PretrainEngine(precision='fp32') serves trunk_backward without d_hidden")
+            return self._trunk_backward_f32(st, d_seq, d_pooled, bool(accumulate))
         m, bufs, acc = self.model, st.bufs, bool(accumulate)
         B, S, H, M, Mr, lay = st.B, st.S, st.H, st.M, st.Mr, st.lay
         g32 = bufs.g_seq32[:Mr]
@@ -934,6 +960,17 @@ class PretrainEngine(object):
             if getattr(m.bert, "use_img_layernorm", None):
                 self._grad(m.bert.LayerNorm.weight).zero_()
                 self._grad(m.bert.LayerNorm.bias).zero_()
+
+    def _trunk_backward_f32(self, st, d_seq, d_pooled, acc):
+        m = self.model
+        g = (torch.zeros((st.M, st.H), dtype=torch.float32, device=st.dev) if d_seq is None
+             else d_seq.detach().reshape(st.M, st.H).float().clone())
+        if d_pooled is not None:
+            training_f32.pooler_backward(self, st, g, d_pooled.detach().float(), acc)
+        elif not acc:
+            self._grad(m.bert.pooler.dense.weight).zero_()
+            self._grad(m.bert.pooler.dense.bias).zero_()
+        training_f32.trunk_backward(self, st, g, acc)
 
     # ---- the launch sequences of vt_encoder_forward/backward_bf16 issued op by op (bench.py's per-kernel timing)
     def _encoder_forward_unrolled(self, bufs, x0, mask, B, S, p_h=0.0, p_a=0.0, seed=0, lay=None, mask_additive=False,
@@ -1123,7 +1160,7 @@ class PretrainEngine(object):
                                t_total=self.t_total,
                                # what travelled in the gradient all-reduce of the run that wrote this state (recorded, not
                                # restored: it is a property of the launch, and it changes the result at rounding level)
-                               grad_comm_dtype=self.grad_comm_dtype, world_size=self.world,
+                               grad_comm_dtype=self.grad_comm_dtype, world_size=self.world, precision=self.precision,
                                hidden_dropout=float(self.cfg.hidden_dropout_prob),
                                attention_dropout_configured=float(self.cfg.attention_probs_dropout_prob),
                                attention_dropout_effective=self.attention_dropout_effective))
