@@ -160,3 +160,114 @@ def inject_dropout_masks(ref, p_hidden, p_attn, seed, B, T, R, device="cuda:0", 
         setmod(pre + "attention.output.dropout", FixedMaskDropout(rows_site(ops.site_selfout(l)), p_hidden))
         setmod(pre + "output.dropout", FixedMaskDropout(rows_site(ops.site_out(l)), p_hidden))
     return ref
+
+
+# ---- which layer loop an eval forward takes -----------------------------------------------------------------------------
+# The test session sends every eval forward through the deferred-LayerNorm loop (tests/conftest.py: threshold 0); the product
+# sends those below DEFERRED_LN_MIN_ROWS_DEFAULT token rows through the seven-launch layer.  The inference comparisons are
+# written once, as bodies that take a Route, and run under both: Route() is the session's setting and changes nothing;
+# Route(shipped=True) sets the shipped threshold on every model the body builds, marks every check name and PROVES the route
+# of every call (tests/test_gpu_shipped_routes.py).
+SHIPPED_SUFFIX = " [shipped route]"
+
+
+def _leaves(out):
+    if isinstance(out, torch.Tensor):
+        return [out]
+    if isinstance(out, (tuple, list)):
+        return [t for o in out for t in _leaves(o)]
+    if isinstance(out, dict):
+        return [t for k in sorted(out) for t in _leaves(out[k])]
+    return [] if out is None else [torch.as_tensor(out)]
+
+
+def same_bits(a, b):
+    """Two (nested) outputs hold the same values bit for bit (NaN equal to NaN: the 7-tuple's corners)."""
+    la, lb = _leaves(a), _leaves(b)
+    return len(la) == len(lb) and all(x.shape == y.shape and x.dtype == y.dtype
+                                      and torch.equal(torch.nan_to_num(x.float(), nan=12345.0), torch.nan_to_num(y.float(), nan=12345.0))
+                                      and torch.equal(torch.isnan(x.float()), torch.isnan(y.float())) for x, y in zip(la, lb))
+
+
+def _clone(out):
+    if isinstance(out, torch.Tensor):
+        return out.clone()
+    if isinstance(out, (tuple, list)):
+        return type(out)(_clone(o) for o in out)
+    return out
+
+
+def encoder_of(model):
+    from visitron_amd.modeling import CaptionBertEncoder
+
+    encs = [m for m in model.modules() if isinstance(m, CaptionBertEncoder)]
+    assert len(encs) == 1, "one trunk per model"
+    return encs[0]
+
+
+class Route(object):
+    def __init__(self, shipped=False):
+        self.shipped = shipped
+        self.suffix = SHIPPED_SUFFIX if shipped else ""
+        self.proven = []          # (rows, "seven-launch layer" | "same route under both thresholds") per call, shipped only
+
+    def name(self, s):
+        return s + self.suffix
+
+    def check(self, name, got, want, bound, kind="maxabs"):
+        return check_close(name + self.suffix, got, want, bound, kind)
+
+    def apply(self, model):
+        """The shipped threshold on `model`'s encoder (the session's stays otherwise).  Returns the model."""
+        if self.shipped:
+            from visitron_amd.modeling import DEFERRED_LN_MIN_ROWS_DEFAULT
+
+            encoder_of(model).deferred_ln_min_rows = DEFERRED_LN_MIN_ROWS_DEFAULT
+        return model
+
+    def call(self, model, rows, fn, history=None):
+        """fn() -- one eval forward of `model` over `rows` token rows (the count the product's rule sees: padded B x S, or
+        the kept rows of a compacted forward).  Session route: fn() as it is.  Shipped route: the rule is asked under both
+        thresholds.  Where they agree (history states, per-layer outputs, >= the threshold's rows) the case has run on this
+        very route in the session's test already: None is returned and the caller moves on.  Where they differ the shipped
+        answer must be the seven-launch layer, fn() runs, and its output must equal, bit for bit, a second run with
+        `deferred_ln = False` -- and every serves_deferred_ln call the product made on the way must have asked for `rows`."""
+        if not self.shipped:
+            return fn()
+        from visitron_amd.modeling import DEFERRED_LN_MIN_ROWS_DEFAULT
+
+        enc = encoder_of(model)
+        assert enc.deferred_ln_min_rows == DEFERRED_LN_MIN_ROWS_DEFAULT and enc.deferred_ln, "Route.apply() the model first"
+        shipped = enc.serves_deferred_ln(history=history, rows=rows)
+        enc.deferred_ln_min_rows = 0
+        session = enc.serves_deferred_ln(history=history, rows=rows)
+        enc.deferred_ln_min_rows = DEFERRED_LN_MIN_ROWS_DEFAULT
+        if shipped is session:
+            assert shipped is (history is None and not enc.output_attentions and not enc.output_hidden_states), rows
+            assert shipped is False or rows >= DEFERRED_LN_MIN_ROWS_DEFAULT
+            self.proven.append((rows, "same route under both thresholds"))
+            print("ROUTE %d rows: %s under both thresholds -- not run twice" % (
+                rows, "deferred-LayerNorm loop" if shipped else "seven-launch layer"))
+            return None
+        assert shipped is False and session is True and rows < DEFERRED_LN_MIN_ROWS_DEFAULT, rows
+        asked, rule = [], enc.serves_deferred_ln
+
+        def spy(history=None, seq=None, rows=None):
+            asked.append((rows, rule(history=history, seq=seq, rows=rows)))
+            return asked[-1][1]
+
+        enc.serves_deferred_ln = spy
+        try:
+            out = _clone(fn())     # (a copy: outputs may live in a workspace the next call rewrites)
+        finally:
+            del enc.serves_deferred_ln
+        assert asked and all(a == (rows, False) for a in asked), (rows, asked)
+        enc.deferred_ln = False
+        try:
+            seven = fn()
+        finally:
+            enc.deferred_ln = True
+        assert same_bits(out, seven), "%d rows: not the seven-launch layer's output" % rows
+        self.proven.append((rows, "seven-launch layer"))
+        print("ROUTE %d rows: seven-launch layer (bitwise equal to deferred_ln = False)" % rows)
+        return out

@@ -818,13 +818,13 @@ def test_small_inference_forwards_take_the_seven_launch_layer(dev):
     from oracle.modeling import BertImgModelwithLocationEmbeds as OTrunk
     from helpers import check_close, model_pair
     from visitron_amd.config import BertConfig
-    from visitron_amd.modeling import BertImgModelwithLocationEmbeds
+    from visitron_amd.modeling import DEFERRED_LN_MIN_ROWS_DEFAULT, BertImgModelwithLocationEmbeds
     from visitron_amd.synth import make_batch
 
     cfg = BertConfig(num_hidden_layers=3, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
     ref, prod = model_pair(OTrunk, BertImgModelwithLocationEmbeds, cfg, seed=2, device=dev)
     enc = prod.encoder
-    enc.deferred_ln_min_rows = 2800                       # the product's default (the test session sets 0: tests/conftest.py)
+    enc.deferred_ln_min_rows = DEFERRED_LN_MIN_ROWS_DEFAULT                 # the product's default (the test session sets 0: tests/conftest.py)
     keys = ("input_ids", "token_type_ids", "attention_mask", "img_feats", "img_location_embeddings")
     for B, deferred in ((2, False), (13, True)):
         b = make_batch(cfg, B, seed=5, with_labels=False)

@@ -20,7 +20,10 @@ built:
   the master's `.grad` (on `device_ids[0]`) and clears them -- what `torch.nn.DataParallel`'s broadcast backward does.
 
 `device_ids` may name one device several times (`[0, 0]`): a rehearsal of the whole mechanism on one GPU, which is how the
-tests run it (tests/test_gpu_round6.py); on distinct devices the copies and the gather cross xGMI.  One process per GPU
+tests run it (tests/test_gpu_round6.py); on distinct devices the copies and the gather cross xGMI.  The distinct-device
+path has NOT been executed on hardware yet: the cross-device weight copy, the gather across devices, the end-of-backward
+gradient move and the library's per-device state have only been rehearsed on one GPU (the `[0, 1]` tests skip without a
+second device).  One process per GPU
 (DistributedDataParallel / PretrainEngine with torch.distributed) remains the faster mode and the one
 bench.py measures: this mode pays the weight refresh (440 MB per replica and step at the base config) and a serial gradient
 reduction on device 0."""
@@ -92,6 +95,7 @@ class DataParallel(nn.Module):
         self.src_device = torch.device("cuda", ids[0])
         object.__setattr__(self, "_replicas", None)       # not sub-modules: parameters() / state_dict() show the master only
         object.__setattr__(self, "_reduce_pending", False)
+        object.__setattr__(self, "_refreshed", None)      # (master's weight key, replicas covered) of the last eval refresh
 
     # ---- replicas -------------------------------------------------------------------------------------------------
     def _check_master(self):
@@ -115,6 +119,11 @@ class DataParallel(nn.Module):
             pr.requires_grad_(pm.requires_grad)
         if _is_fp32(self.module):
             set_precision(r, "fp32")
+        # the routing switches a caller may have set on the master's encoder(s) are not part of the state dict
+        for mm, mr in zip(self.module.modules(), r.modules()):
+            for attr in ("deferred_ln", "deferred_ln_min_rows", "precise_final"):
+                if hasattr(mm, attr):
+                    setattr(mr, attr, getattr(mm, attr))
         return r
 
     def replicas(self):
@@ -125,8 +134,28 @@ class DataParallel(nn.Module):
                                [self.module] + [self._build_replica(torch.device("cuda", d)) for d in self.device_ids[1:]])
         return self._replicas
 
+    def _master_key(self):
+        """What the packed-weight caches key on (modeling._param_key: the process-wide generation + every parameter's
+        address and version), over the master's parameters and buffers."""
+        from .modeling import _param_key
+
+        return _param_key(list(self.module.parameters()) + list(self.module.buffers()))
+
     def _refresh(self, reps):
-        """Parameters, buffers and mode of the master into every other replica (one multi-tensor copy each)."""
+        """Parameters, buffers and mode of the master into every other replica (one multi-tensor copy each).
+
+        Training mode: before every forward (the optimizer has stepped in between; the autograd bridge drops the packed
+        weight copies itself).  Eval mode: only when the master's weights have changed since the last refresh (or a replica
+        has not been refreshed yet) -- the copy goes through `p.data`, which moves neither the replicas' versions nor the
+        generation, so the replicas' packed bf16 copies are dropped here, with everyone else's in the process
+        (modeling.invalidate_packed_weights); unchanged weights copy nothing and repack nothing."""
+        from .modeling import invalidate_packed_weights
+
+        training = self.module.training
+        if not training and self._refreshed is not None:
+            key, covered = self._refreshed
+            if covered >= len(reps) and key == self._master_key():
+                return
         src_p = [p.data for p in self.module.parameters()]
         src_b = [b.data for b in self.module.buffers()]
         for r in reps[1:]:
@@ -134,8 +163,13 @@ class DataParallel(nn.Module):
                 torch._foreach_copy_([p.data for p in r.parameters()], src_p)
                 if src_b:
                     torch._foreach_copy_([b.data for b in r.buffers()], src_b)
-            if r.training != self.module.training:
-                r.train(self.module.training)
+            if r.training != training:
+                r.train(training)
+        if training:
+            object.__setattr__(self, "_refreshed", None)      # the first eval forward after training refreshes again
+        else:
+            invalidate_packed_weights()
+            object.__setattr__(self, "_refreshed", (self._master_key(), len(reps)))
 
     # ---- gradients ------------------------------------------------------------------------------------------------
     def _reduce_grads(self):
