@@ -160,9 +160,14 @@ int vt_debug_dropout_mask(uint8_t* out, int64_t n, float drop_p, uint64_t drop_s
  * caller's raw 2-D mask as fp32 [B,S] (null = all ones) when mask_additive == 0 -- the -10000
  * arithmetic of tasks/viewpoint_select/encoder.py:238-241 then happens in the kernel -- or the
  * already-additive [B,S] bias when mask_additive == 1 (what CaptionBertEncoder.forward receives), or an additive
- * per-query bias [B,S,S] when mask_additive == 2 (the reference's 3-D attention_mask, encoder.py:226-229; forward and
- * vt_attention_probs_f32 only, the backward returns VT_ERR_UNSUPPORTED).  lse (optional, [B,nh,S]) gets
+ * per-query bias [B,S,S] when mask_additive == 2 (the reference's 3-D attention_mask, encoder.py:226-229; the backward
+ * serves it through its 4- and 8-wave kernels, never together with compacted rows).  lse (optional, [B,nh,S]) gets
  * the natural-log log-sum-exp of the masked scores for the backward pass.
+ * Infinite biases: an additive bias of -inf, or one whose product with 8 overflows (torch.finfo(float32).min), gives its
+ * key the probability exactly 0 in the forward, the probabilities and the backward, provided the query row keeps at least
+ * one finite key.  A row with NO finite key is outside the contract (the reference's softmax is NaN there too): the forward
+ * returns NaN for that context row and lse = -inf, and the backward's dq / dk / dv of that (batch, head) are unspecified
+ * (other batches and heads are not affected).
  * keep_bits (optional; training with drop_p > 0): the kernel also writes its keep decisions, one word per (32-query block,
  * key): keep_bits[((b*nh + h) * nqb + qb) * kpitch + key], bit j = keep(query 32 qb + j, key), nqb = ceil(S/32),
  * kpitch = 32 nqb (VT_KEEP_WORDS(B, nh, S) words).  The backward kernels read them back instead of re-deriving the mask

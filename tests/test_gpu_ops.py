@@ -192,7 +192,7 @@ def test_attention_matches_fp32(dev, B, S, nh):
     mask = (torch.rand(B, S, generator=g) > 0.25).float()
     mask[:, 0] = 1.0
     if B > 1:
-        mask[1] = 0.0  # a fully masked sequence: uniform attention, as the -10000 arithmetic gives
+        mask[1] = 0.0  # a fully masked sequence: every key shifted by -10000, i.e. the softmax of the raw scores
     t = qkv.view(B, S, 3, nh, 64).permute(2, 0, 3, 1, 4)
     want = _attention_ref(t[0], t[1], t[2], (1.0 - mask) * -10000.0).permute(0, 2, 1, 3).reshape(B * S, H)
     lse = torch.zeros((B, nh, S), dtype=torch.float32, device=dev)

@@ -138,7 +138,12 @@ __global__ __launch_bounds__(512, 4) void attention_fwd_d64(AttnArgs a) {
   f32x16 o0, o1;
 #pragma unroll
   for (int i = 0; i < 16; ++i) { o0[i] = 0.f; o1[i] = 0.f; }
-  float m_run = -INFINITY, l_run = 0.f;   // running maximum (of the raw accumulators) and running sum
+  // running maximum (of the raw accumulators) and running sum.  The maximum starts at the lowest FINITE float, not at -inf: a
+  // tile whose keys all carry a bias of -inf (an additive mask of -inf, or of finfo(float32).min, which bias / scale
+  // overflows) leaves it where it is, negm = -m_run * scale2 stays finite and every p of the tile is exp2(-inf) = 0 -- from
+  // -inf the same tile gave exp2(-inf + inf) = NaN.  The first finite score rescales by exp2((m_run - m_new) * scale2) = 0
+  // exactly as it did from -inf (l_run and the outputs are still 0), so no result with finite biases changes.
+  float m_run = -3.402823466e+38f, l_run = 0.f;
   const float scale2 = a.scale * LOG2E;
   const float inv_scale = 1.0f / a.scale;
   DropCfg dr = a.drop;
