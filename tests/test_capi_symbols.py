@@ -1,8 +1,11 @@
 """CPU: the C-ABI library loads and exports every function include/visitron_hip.h declares, and the
-ctypes binding lists exactly those (no compute calls without a GPU)."""
+ctypes binding, which is derived from that header, lists exactly those with the types written out here
+(no compute calls without a GPU)."""
 import ctypes
 import os
 import re
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -46,3 +49,84 @@ def test_struct_layouts_match_the_header():
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         fields = re.findall(r"(?:\*|int32_t)\s*([a-z0-9_]+)\s*;", body)
         assert fields == [f[0] for f in cls._fields_], struct
+
+
+# ---- the binding is derived from the header: pin the derivation from outside, with literals ----------------------------
+_P, _I, _L, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+_DROP = [_F, ctypes.c_uint64, ctypes.c_uint32]   # (p, step seed, site)
+
+
+def _struct_ptr(name):
+    from visitron_amd import _lib
+
+    return ctypes.POINTER(getattr(_lib, name))
+
+
+def _pinned():
+    """name -> (restype, argtypes), written by hand from include/visitron_hip.h: one entry per rule of the binding."""
+    return {
+        # const char* return; int64_t, float and void returns
+        "vt_error_string": (ctypes.c_char_p, [_I]),
+        "vt_gemm_workspace_region_bytes": (_L, []),
+        "vt_attn_dropout_effective": (_F, [_F]),
+        "vt_gemm_tune": (None, [_I, _I, _I, _I, _I]),
+        # the dropout triple (float, uint64_t, uint32_t) and vt_stream_t
+        "vt_apply_dropout_bf16": (_I, [_P, _L, _L, _I] + _DROP + [_P]),
+        # unsigned*
+        "vt_wgrad_turn_timeouts": (_I, [ctypes.POINTER(ctypes.c_uint)]),
+        # pointers to the mirrored structs (all seven over these four entries)
+        "vt_encoder_backward_seq_bf16": (_I, [
+            _struct_ptr("LayerWeights"), _struct_ptr("LayerWeightsT"), _struct_ptr("LayerActs"), _struct_ptr("LayerGrads"),
+            _I, _P, _P, _struct_ptr("BwdWorkspace"), _struct_ptr("BwdWorkspace"), _I, _I, _I, _I, _I, _F, _I, _F, _F,
+            ctypes.c_uint64, _I, _L, _P, _P, _P, _P]),
+        "vt_encoder_forward_ln_bf16": (_I, [_struct_ptr("LayerWeightsLn"), _I] + [_P] * 10 + [
+            _I, _P, _I, _I, _I, _I, _I, _F, _L, _P]),
+        "vt_wgrad_bf16": (_I, [_struct_ptr("WgradProblem"), _I, _I, _P]),
+        # pointer to pointer, const in every position
+        "vt_transpose_batch_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
+        # the longest list: 34 arguments
+        "vt_gemm_f32_ex": (_I, [_P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _P, _P, _L, _P, _L, _L, _L, _P, _I, _I, _I, _I, _F,
+                                _I, _I, _I, _I, _I, _I, _P, _F, ctypes.c_uint64, ctypes.c_uint32, _P]),
+    }
+
+
+def test_derived_signatures_match_the_written_ones():
+    from visitron_amd import _lib
+
+    lib = _lib.load()
+    for name, (restype, argtypes) in _pinned().items():
+        got_res, got_args = _lib.SIGNATURES[name]
+        assert got_res is restype, name
+        assert len(got_args) == len(argtypes), name
+        assert got_args == argtypes, name
+        fn = getattr(lib, name)   # and load() installs exactly that on the symbol
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+
+
+def test_struct_sizes_and_offsets_are_the_abi():
+    from visitron_amd import _lib
+
+    # the same seven numbers are static_asserts beside the includes of visitron_amd/csrc/capi.hip
+    sizes = {"LayerWeights": 96, "LayerActs": 136, "LayerWeightsLn": 96, "LayerWeightsT": 32, "LayerGrads": 96,
+             "BwdWorkspace": 80, "WgradProblem": 72}
+    for name, size in sizes.items():
+        cls = getattr(_lib, name)
+        assert issubclass(cls, ctypes.Structure) and cls.__name__ == name
+        assert ctypes.sizeof(cls) == size, name
+    # first non-pointer field of the two structs that have one
+    assert _lib.WgradProblem.ldy.offset == 8 and _lib.WgradProblem.ldy.size == 8
+    assert _lib.WgradProblem.N.offset == 56 and _lib.WgradProblem.accumulate.offset == 64
+    assert _lib.LayerActs.ln_residual_mode.offset == 128 and _lib.LayerActs.ln_residual_mode.size == 4
+    assert _lib.LayerActs.reserved0.offset == 132
+
+
+def test_binding_refuses_what_it_has_no_rule_for(monkeypatch, tmp_path):
+    from visitron_amd import _lib
+
+    for base, stars in (("double", ""), ("size_t", ""), ("char", "*"), ("vt_layer_acts", "**"), ("unsigned", "")):
+        with pytest.raises(ImportError, match="no ctypes rule"):
+            _lib._ctype(base, stars, "int vt_x(%s%s a)" % (base, stars))
+    missing = str(tmp_path / "include" / "visitron_hip.h")
+    monkeypatch.setattr(_lib, "_HEADER", missing)
+    with pytest.raises(ImportError, match=re.escape(missing)):
+        _lib._parse_header()

@@ -196,7 +196,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_bf16_v10(GemmArgs g) {
 }
 
 // Two workgroups per compute unit (72 KiB of LDS, <= 256 registers each)
-int vt_gemm_persistent_cus();   // gemm_v7.hip: compute units the persistent grids may use (vt_gemm_reserve_cus)
 
 template <int ACT, bool OUT_F32>
 static int launch_v10(const GemmArgs& g, hipStream_t stream) {

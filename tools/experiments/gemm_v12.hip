@@ -189,9 +189,6 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_bf16_v12(GemmArgs g) {
   if (tr && tid == 0) { tr[62] = __builtin_amdgcn_s_memrealtime(); tr[63] = __builtin_amdgcn_s_memtime(); }
 }
 
-int vt_gemm_persistent_cus();   // gemm_v7.hip
-int vt_gemm_v8_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stream, int mtn);
-
 template <int ACT, int MTN>
 static int launch_v12(const GemmArgs& g, hipStream_t stream) {
   GemmArgs ga = g;

@@ -5,6 +5,7 @@ op in ``visitron_amd.ops`` refuses tensors that are not on a HIP device.
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libvisitron_hip.so")
@@ -13,226 +14,85 @@ LIB_PATH = os.environ.get("VT_HIP_LIB", LIB_PATH)   # A/B builds of the kernels 
 # error codes of include/visitron_hip.h
 VT_OK, VT_ERR_BAD_SHAPE, VT_ERR_BAD_ALIGN, VT_ERR_NULL, VT_ERR_UNSUPPORTED, VT_ERR_HIP = 0, -1, -2, -3, -4, -5
 
-c_void_p, c_int, c_int64, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-c_uint64, c_uint32 = ctypes.c_uint64, ctypes.c_uint32
-DROP = [c_float, c_uint64, c_uint32]  # (p, step seed, site)
+# ---- the binding is read from the header: one declaration per entry point and struct, in include/visitron_hip.h ----------
+_HEADER = os.path.join(os.path.dirname(_HERE), "include", "visitron_hip.h")
+
+# C struct -> name of the ctypes.Structure mirroring it (module attributes, set below)
+_STRUCTS = {"vt_layer_weights": "LayerWeights", "vt_layer_acts": "LayerActs", "vt_layer_weights_ln": "LayerWeightsLn",
+            "vt_layer_weights_t": "LayerWeightsT", "vt_layer_grads": "LayerGrads", "vt_bwd_workspace": "BwdWorkspace",
+            "vt_wgrad_problem": "WgradProblem"}
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+            "uint32_t": ctypes.c_uint32, "float": ctypes.c_float, "vt_stream_t": ctypes.c_void_p}
+_POINTEES = ("void", "float", "int", "int32_t", "int64_t", "uint8_t", "uint16_t", "uint32_t", "uint64_t")  # data: c_void_p
+_classes = {}   # C struct name -> Structure class, filled by _parse_header
+_DECL = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\s*)?)*)(\w+(?:\s*,\s*\w+)*)")   # [const] base [*...] name[, name]
 
 
-class LayerWeights(ctypes.Structure):  # vt_layer_weights
-    _fields_ = [(n, c_void_p) for n in (
-        "w_qkv", "b_qkv", "w_ao", "b_ao", "ln1_g", "ln1_b", "w_in", "b_in", "w_out", "b_out", "ln2_g", "ln2_b")]
+def _ctype(base, stars, what):
+    """The closed type rule; anything outside it raises with the declaration's text."""
+    stars = stars.count("*")
+    if stars == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if stars == 1 and base in _classes:
+        return ctypes.POINTER(_classes[base])
+    if stars == 1 and base == "unsigned":
+        return ctypes.POINTER(ctypes.c_uint)
+    if stars >= 1 and base in _POINTEES:
+        return ctypes.c_void_p
+    raise ImportError("visitron_amd: no ctypes rule for `%s` in %s" % (" ".join(what.split()), _HEADER))
 
 
-class LayerActs(ctypes.Structure):  # vt_layer_acts
-    _fields_ = [(n, c_void_p) for n in (
-        "qkv", "ctx", "attn_pre", "attn_out", "mid_pre", "mid", "out_pre", "out", "lse",
-        "ln1_mean", "ln1_rstd", "ln2_mean", "ln2_rstd", "keep_bits", "ln1_h", "ln2_h")] + [
-        ("ln_residual_mode", ctypes.c_int32), ("reserved0", ctypes.c_int32)]
+def _parse_header():
+    """include/visitron_hip.h -> _classes (the seven Structure classes) and {name: (restype, argtypes)}."""
+    if not os.path.exists(_HEADER):
+        raise ImportError("visitron_amd: %s not found: the ctypes binding is derived from it" % _HEADER)
+    src = open(_HEADER).read()
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    src = re.sub(r"#ifdef __cplusplus.*?#endif", " ", src, flags=re.S)   # the extern "C" braces
+    src = re.sub(r"^[ \t]*#.*$", " ", src, flags=re.M)
+
+    def struct(m):
+        if m.group(1) != m.group(3) or m.group(1) not in _STRUCTS:
+            raise ImportError("visitron_amd: struct %s of %s has no ctypes mirror" % (m.group(1), _HEADER))
+        fields = []
+        for decl in filter(None, (d.strip() for d in m.group(2).split(";"))):
+            f = _DECL.fullmatch(decl)
+            if not f or ("," in f.group(3) and f.group(2)):
+                raise ImportError("visitron_amd: cannot read field `%s` of %s in %s" % (decl, m.group(1), _HEADER))
+            fields += [(n.strip(), _ctype(f.group(1), f.group(2), decl)) for n in f.group(3).split(",")]
+        _classes[m.group(1)] = type(_STRUCTS[m.group(1)], (ctypes.Structure,), {"_fields_": fields})
+        return " "
+
+    src = re.sub(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", struct, src, flags=re.S)
+    if len(_classes) != len(_STRUCTS):
+        raise ImportError("visitron_amd: %s does not define %s" % (_HEADER, ", ".join(sorted(set(_STRUCTS) - set(_classes)))))
+    signatures = {}
+    for stmt in filter(None, (s.strip() for s in src.split(";"))):
+        if stmt == "typedef void* vt_stream_t":
+            continue
+        p = re.fullmatch(r"(const\s+char\s*\*|\w+)\s*(vt_\w+)\s*\((.*)\)", stmt, flags=re.S)
+        if not p or p.group(2) in signatures:
+            raise ImportError("visitron_amd: cannot read `%s` in %s" % (" ".join(stmt.split()), _HEADER))
+        ret, name, params = p.groups()
+        if ret.startswith("const"):
+            restype = ctypes.c_char_p
+        else:
+            restype = None if ret == "void" else _ctype(ret, "", stmt)
+        argtypes = []
+        if params.strip() != "void":
+            for param in params.split(","):
+                a = _DECL.fullmatch(param.strip())
+                if not a or "," in a.group(3):
+                    raise ImportError("visitron_amd: cannot read `%s` in %s" % (" ".join(stmt.split()), _HEADER))
+                argtypes.append(_ctype(a.group(1), a.group(2), stmt))
+        signatures[name] = (restype, argtypes)
+    return signatures
 
 
-class LayerWeightsLn(ctypes.Structure):  # vt_layer_weights_ln
-    _fields_ = [(n, c_void_p) for n in (
-        "w_qkv", "g_qkv", "h_qkv", "w_ao", "cb_ao", "gamma_in", "w_in", "g_in", "h_in", "w_out", "cb_out", "ln1_g")]
-
-
-class LayerWeightsT(ctypes.Structure):  # vt_layer_weights_t
-    _fields_ = [(n, c_void_p) for n in ("wt_qkv", "wt_ao", "wt_in", "wt_out")]
-
-
-class LayerGrads(ctypes.Structure):  # vt_layer_grads
-    _fields_ = [(n, c_void_p) for n in (
-        "d_w_qkv", "d_b_qkv", "d_w_ao", "d_b_ao", "d_ln1_g", "d_ln1_b", "d_w_in", "d_b_in", "d_w_out", "d_b_out",
-        "d_ln2_g", "d_ln2_b")]
-
-
-class BwdWorkspace(ctypes.Structure):  # vt_bwd_workspace
-    _fields_ = [(n, c_void_p) for n in ("g_pre", "g_pre2", "g_mid", "g_ctx", "g_qkv", "delta", "ln_partial", "dq32",
-                                        "g_pre_d", "g_pre2_d")]
-
-
-class WgradProblem(ctypes.Structure):  # vt_wgrad_problem
-    _fields_ = [("dY", c_void_p), ("ldy", c_int64), ("X", c_void_p), ("ldx", c_int64), ("dW", c_void_p),
-                ("ldw", c_int64), ("db", c_void_p), ("N", c_int), ("K", c_int), ("accumulate", c_int)]
-
-
-# name -> (restype, argtypes); must list every symbol declared in include/visitron_hip.h
-SIGNATURES = {
-    "vt_error_string": (ctypes.c_char_p, [c_int]),
-    "vt_abi_version": (c_int, []),
-    "vt_center_mask": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_void_p]),
-    "vt_batch_row_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "vt_batch_row_lists": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p,
-                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vt_action_head_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_float, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
-    "vt_linear_splitk_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int,
-                                      c_void_p]),
-    "vt_embed_table_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int64, c_int64,
-                                    c_void_p, c_void_p, c_void_p]),
-    "vt_debug_set_gemm_variant": (None, [c_int]),
-    "vt_debug_set_gemm_trace": (None, [c_void_p]),
-    "vt_debug_set_wgrad_kernel": (None, [c_int]),
-    "vt_gemm_tune": (None, [c_int, c_int, c_int, c_int, c_int]),
-    "vt_debug_set_attn_bwd_waves": (None, [c_int]),
-    "vt_set_weight_prefetch": (c_int, [c_int, c_int]),
-    "vt_get_weight_prefetch": (c_int, [c_int]),
-    "vt_set_attn_dropout_bits": (c_int, [c_int]),
-    "vt_get_attn_dropout_bits": (c_int, []),
-    "vt_attn_dropout_effective": (ctypes.c_float, [ctypes.c_float]),
-    "vt_gemm_reserve_cus": (None, [c_int]),
-    "vt_gemm_set_workspace": (c_int, [c_void_p, c_int64]),
-    "vt_gemm_workspace_region_bytes": (c_int64, []),
-    "vt_gemm_shared_tile_timeouts": (c_int, [ctypes.POINTER(ctypes.c_uint)]),
-    "vt_step_counters": (c_int, [c_void_p, c_void_p]),
-    "vt_linear_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
-                               c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "vt_linear_bf16_ex": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
-                                  c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int] + DROP + [c_void_p]),
-    "vt_linear_lnres_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
-                                     c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int] + DROP + [c_void_p]),
-    "vt_apply_dropout_bf16": (c_int, [c_void_p, c_int64, c_int64, c_int] + DROP + [c_void_p]),
-    "vt_debug_dropout_mask": (c_int, [c_void_p, c_int64] + DROP + [c_int, c_void_p]),
-    "vt_attention_probs_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                       c_int, c_void_p]),
-    "vt_attention_bwd_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int,
-                                      c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int]
-                              + DROP + [c_void_p, c_void_p]),
-    "vt_layernorm_bwd_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
-                                      c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_int64] + DROP
-                              + [c_void_p]),
-    "vt_layernorm_bwd_h_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
-                                        c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_int64] + DROP
-                                + [c_void_p]),
-    "vt_embed_layernorm_bwd": (c_int, [c_void_p] * 8 + [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                        c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_float, c_uint64, c_void_p]),
-    "vt_adamw_flat": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float,
-                              c_float, c_float, c_float, c_float, c_void_p]),
-    "vt_adamw_flat_g16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float,
-                                  c_float, c_float, c_float, c_float, c_void_p]),
-    "vt_cast_f32_to_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p]),
-    "vt_scale_heads_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
-    "vt_mask_tokens": (c_int, [c_void_p] * 10 + [c_int64, c_int64, c_int64, c_float, c_void_p]),
-    "vt_assemble_regions": (c_int, [c_void_p] * 13 + [c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "vt_ce_softmax_rows": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int,
-                                   c_int, c_float, c_void_p]),
-    "vt_ce_double_softmax_rows": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int,
-                                   c_int, c_float, c_void_p]),
-    "vt_lstm_step_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
-                                 c_int, c_int, c_int, c_void_p]),
-    "vt_lstm_sequence_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                     c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
-    "vt_lstm_sequence_persistent_ws_bytes": (c_int64, [c_int, c_int]),
-    "vt_lstm_sequence_persistent_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int64,
-                                                c_void_p]),
-    "vt_skinny_linear_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p,
-                                     c_int64, c_int, c_int, c_int, c_int, c_void_p]),
-    "vt_lstm_sequence_rows_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                          c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
-    "vt_lstm_step_train_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
-                                       c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vt_lstm_sequence_train_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                           c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                           c_void_p, c_int64, c_void_p]),
-    "vt_lstm_step_bwd_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
-                                     c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_int,
-                                     c_int, c_void_p]),
-    "vt_lstm_sequence_bwd_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
-    "vt_softdot_attention_bwd_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
-                                             c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "vt_softdot_attention_bwd_split_ws_floats": (c_int64, [c_int, c_int, c_int]),
-    "vt_softdot_attention_bwd_split_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
-                                                   c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "vt_softdot_attention_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                         c_int, c_int, c_void_p]),
-    "vt_transpose_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p]),
-    "vt_transpose_batch_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "vt_dgelu_mul_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "vt_encoder_backward_bf16": (c_int, [ctypes.POINTER(LayerWeights), ctypes.POINTER(LayerWeightsT),
-                                         ctypes.POINTER(LayerActs), ctypes.POINTER(LayerGrads), c_int, c_void_p,
-                                         c_void_p, c_int, c_void_p, ctypes.POINTER(BwdWorkspace), c_int, c_int, c_int,
-                                         c_int, c_int, c_float, c_int, c_float, c_float, c_uint64, c_int, c_void_p]),
-    "vt_encoder_backward_overlap_bf16": (c_int, [ctypes.POINTER(LayerWeights), ctypes.POINTER(LayerWeightsT),
-                                                 ctypes.POINTER(LayerActs), ctypes.POINTER(LayerGrads), c_int, c_void_p,
-                                                 c_void_p, c_int, c_void_p, ctypes.POINTER(BwdWorkspace),
-                                                 ctypes.POINTER(BwdWorkspace), c_int, c_int, c_int, c_int, c_int, c_float,
-                                                 c_int, c_float, c_float, c_uint64, c_int, c_void_p, c_void_p]),
-    "vt_attention_fwd_seq_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int]
-                                  + DROP + [c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vt_attention_bwd_seq_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
-                                          c_int64, c_void_p, c_int, c_int, c_int, c_int] + DROP
-                                  + [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
-    "vt_encoder_forward_seq_bf16": (c_int, [ctypes.POINTER(LayerWeights), ctypes.POINTER(LayerActs), c_int, c_void_p, c_void_p,
-                                            c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_uint64, c_int64,
-                                            c_void_p, c_void_p, c_void_p]),
-    "vt_encoder_backward_seq_bf16": (c_int, [ctypes.POINTER(LayerWeights), ctypes.POINTER(LayerWeightsT),
-                                             ctypes.POINTER(LayerActs), ctypes.POINTER(LayerGrads), c_int, c_void_p, c_void_p,
-                                             ctypes.POINTER(BwdWorkspace), ctypes.POINTER(BwdWorkspace), c_int, c_int, c_int,
-                                             c_int, c_int, c_float, c_int, c_float, c_float, c_uint64, c_int, c_int64,
-                                             c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vt_attention_fwd_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p,
-                                      c_int, c_int, c_int, c_int] + DROP + [c_void_p, c_void_p]),
-    "vt_layernorm_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_int, c_int, c_float, c_int, c_int, c_void_p]),
-    "vt_layernorm_h_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
-                                    c_void_p, c_int, c_int, c_float, c_void_p]),
-    "vt_embed_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                   c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
-                                   c_void_p, c_float, c_uint64, c_void_p]),
-    "vt_pack_concat_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p]),
-    "vt_wgrad_bf16": (c_int, [ctypes.POINTER(WgradProblem), c_int, c_int, c_void_p]),
-    "vt_wgrad_turn_timeouts": (c_int, [ctypes.POINTER(ctypes.c_uint)]),
-    "vt_linear_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
-                              c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p]),
-    "vt_bmm_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p,
-                           c_int64, c_int64, c_int64, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p]),
-    "vt_softmax_rows_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_float, c_void_p, c_int, c_void_p, c_int, c_int,
-                                    c_void_p]),
-    "vt_layernorm_rows": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int,
-                                  c_float, c_int, c_int, c_void_p]),
-    "vt_embed_layernorm_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
-                                       c_void_p, c_void_p]),
-    "vt_gemm_f32_ex": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p,
-                               c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int,
-                               c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_float, c_uint64, c_uint32,
-                               c_void_p]),
-    "vt_gemm_f32_split_count": (c_int, [c_int, c_int, c_int]),
-    "vt_colsum_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p]),
-    "vt_layernorm_bwd_f32_ws_floats": (c_int64, [c_int64, c_int]),
-    "vt_layernorm_bwd_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_float, c_void_p, c_int64,
-                                     c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_float, c_uint32,
-                                     c_float, c_uint32, c_uint64, c_void_p]),
-    "vt_layernorm_drop_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_float, c_int,
-                                      c_int, c_float, c_uint64, c_uint32, c_void_p]),
-    "vt_attn_softmax_train_f32": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_void_p, c_int,
-                                          c_void_p, c_float, c_uint64, c_uint32, c_void_p]),
-    "vt_dgelu_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "vt_embed_sum_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                 c_int, c_int, c_int, c_void_p, c_void_p]),
-    "vt_dropout_rows_f32": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_float, c_uint64,
-                                    c_uint32, c_void_p]),
-    "vt_ce_softmax_rows_g32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int,
-                                       c_float, c_void_p]),
-    "vt_ce_double_softmax_rows_g32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int,
-                                              c_int, c_float, c_void_p]),
-    "vt_action_head_g32": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_float, c_void_p, c_int64, c_int, c_void_p,
-                                   c_void_p]),
-    "vt_linear_ln_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_float,
-                                  c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_int,
-                                  c_int, c_void_p]),
-    "vt_ln_apply": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_int64,
-                            c_void_p, c_int64, c_int64, c_int, c_void_p]),
-    "vt_ln_stream_init": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int64, c_int64,
-                                  c_int, c_float, c_void_p]),
-    "vt_encoder_forward_ln_bf16": (c_int, [ctypes.POINTER(LayerWeightsLn), c_int] + [c_void_p] * 10 + [
-        c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int64, c_void_p]),
-    "vt_encoder_forward_ln_seq_bf16": (c_int, [ctypes.POINTER(LayerWeightsLn), c_int] + [c_void_p] * 9 + [
-        c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
-    "vt_encoder_forward_bf16": (c_int, [ctypes.POINTER(LayerWeights), ctypes.POINTER(LayerActs), c_int, c_void_p,
-                                        c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
-                                        c_float, c_float, c_uint64, c_void_p]),
-}
+# name -> (restype, argtypes) of every entry point the header declares
+SIGNATURES = _parse_header()
+# LayerWeights, LayerActs, LayerWeightsLn, LayerWeightsT, LayerGrads, BwdWorkspace, WgradProblem
+globals().update({_STRUCTS[c]: cls for c, cls in _classes.items()})
 
 _lib = None
 

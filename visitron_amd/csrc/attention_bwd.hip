@@ -22,7 +22,7 @@
 // fp32 atomics into a scratch [B*S,H] slab: each slice's dQ^T is transposed through LDS so that a
 // wave-instruction adds 256 contiguous bytes of one row (the full-rate atomic shape), then a small
 // kernel rounds the slab to bf16.
-#include "common.hpp"
+#include "dispatch.hpp"
 #include <type_traits>
 
 #define LOG2E 1.4426950408889634f
@@ -1482,8 +1482,8 @@ void vt_attn_bwd_set_waves(int w) { g_attn_bwd_waves = (w == 4 || w == 10 || w =
 int vt_attention_bwd_dispatch(const void* qkv, long ld_qkv, const void* dctx, long ld_d, const void* ctx, long ld_ctx,
                               const float* mask, int mask_additive, const float* lse, float* delta_ws, void* dqkv,
                               long ld_dqkv, float* dq32_ws, int B, int S, int nh, int head_size, hipStream_t stream,
-                              const DropCfg* drop = nullptr, const int* seq_start = nullptr, const int* seq_len = nullptr,
-                              long rows_total = 0, const uint32_t* keep_bits = nullptr) {
+                              const DropCfg* drop, const int* seq_start, const int* seq_len, long rows_total,
+                              const uint32_t* keep_bits) {
   if (mask_additive == 2 && (!mask || seq_start)) return VT_ERR_NULL;   // per-query bias [B, S, S]
   if (!qkv || !dctx || !ctx || !lse || !delta_ws || !dqkv) return VT_ERR_NULL;
   if (head_size != 64) return VT_ERR_UNSUPPORTED;

@@ -19,7 +19,7 @@
 // K and V of the (batch, head) are staged once per 256-key chunk by global_load_lds_dwordx4
 // (swizzles applied on the source address).  Online softmax in fp32; the masked score is formed
 // with the reference's roundings (fma(acc, 1/8, mask)) and (score - max) is exact before exp2.
-#include "common.hpp"
+#include "dispatch.hpp"
 
 struct AttnArgs {
   const bf16_t* qkv;        // [B*S, ld_qkv]  q | k | v, each nh*64 wide
@@ -330,8 +330,8 @@ __global__ __launch_bounds__(512, 4) void attention_fwd_d64(AttnArgs a) {
 
 int vt_attention_fwd_dispatch(const void* qkv, long ld_qkv, const float* mask, int mask_additive, const float* head_scale, void* ctx,
                               long ld_ctx, float* lse, int B, int S, int nh, int head_size, hipStream_t stream,
-                              const DropCfg* drop = nullptr, const int* seq_start = nullptr, const int* seq_len = nullptr,
-                              uint32_t* keep_bits = nullptr, const PrefetchArgs* pf = nullptr) {
+                              const DropCfg* drop, const int* seq_start, const int* seq_len, uint32_t* keep_bits,
+                              const PrefetchArgs* pf) {
   if (!qkv || !ctx) return VT_ERR_NULL;
   if (head_size != 64) return VT_ERR_UNSUPPORTED;
   if (B <= 0 || S <= 0 || nh <= 0 || B > 65535 || nh > 65535) return VT_ERR_BAD_SHAPE;

@@ -2,7 +2,7 @@
 // hot path -- tasks/viewpoint_select/data_loader_pretrain.py:549-613 (_mask_tokens) and :615-712 (region features,
 // location embeddings, padding / truncation, label and attention-mask assembly) -- as two HBM-bound kernels over a whole
 // batch.  Integer work: outputs are bit-exact against the per-item restatement (oracle/data.py) on shared random draws.
-#include "common.hpp"
+#include "dispatch.hpp"
 
 // ---- _mask_tokens (data_loader_pretrain.py:549-613), one thread per token ------------------------------------------
 //   masked   = bernoulli(mlm_probability, 0 on special tokens)  [u_mask < p]   | token-class positions (forced)

@@ -1,0 +1,186 @@
+// Every host function and argument block that crosses a translation unit, declared once: the *_dispatch functions
+// and setters each .hip file defines for the C-ABI layer (capi.hip) and for each other.  Default arguments live here
+// and only here.  The launchers that take GemmArgs are in gemm_common.hpp, vt_wgrad_v8_dispatch in wgrad_common.hpp.
+#pragma once
+#include "common.hpp"
+#include "wgrad_common.hpp"
+#include "rollout_args.hpp"
+
+// vt_batch_rows_dispatch (rowops.hip: batch_row_counts / batch_row_lists)
+struct BatchRowsArgs {
+  const long* lab; const long* tl;      // [M] or null
+  const float* mask;                    // [B*S] fp32 or null (no compaction wanted)
+  const int* err;                       // the embedding kernel's flag or null
+  long M; int S; int B;
+  long* counts;                         // [5]: err, n_w, n_t, n_keep, bad   (zeroed by the caller)
+  int* tile_counts;                     // [ntiles][3]: per 1024-position tile (written by the counts kernel, read by the lists kernel)
+  long* idx_w; long* idx_t;             // row lists
+  long* index; long* inverse;           // kept rows; padded position -> compact row or -1
+  int* start; int* length;              // [B]
+  long n_w, n_t, n_keep;                // capacities of the three lists (the counts batch_row_counts reported)
+};
+
+// ---- attention_bwd.hip
+void vt_attn_bwd_set_waves(int w);
+int vt_attention_bwd_dispatch(const void* qkv, long ld_qkv, const void* dctx, long ld_d, const void* ctx, long ld_ctx,
+                              const float* mask, int mask_additive, const float* lse, float* delta_ws, void* dqkv,
+                              long ld_dqkv, float* dq32_ws, int B, int S, int nh, int head_size, hipStream_t stream,
+                              const DropCfg* drop = nullptr, const int* seq_start = nullptr, const int* seq_len = nullptr,
+                              long rows_total = 0, const uint32_t* keep_bits = nullptr);
+
+// ---- attention_fwd.hip
+int vt_attention_fwd_dispatch(const void* qkv, long ld_qkv, const float* mask, int mask_additive, const float* head_scale, void* ctx,
+                              long ld_ctx, float* lse, int B, int S, int nh, int head_size, hipStream_t stream,
+                              const DropCfg* drop = nullptr, const int* seq_start = nullptr, const int* seq_len = nullptr,
+                              uint32_t* keep_bits = nullptr, const PrefetchArgs* pf = nullptr);
+int vt_attention_probs_dispatch(const void* qkv, long ld_qkv, const float* mask, int mask_additive, const float* head_scale,
+                                const float* lse, float* probs, int B, int S, int nh, int head_size, hipStream_t stream);
+
+// ---- datapipe.hip: the data pipeline's token masking and region assembly
+int vt_mask_tokens_dispatch(const int64_t* ids, const uint8_t* special, const int64_t* token_classes, const float* u_mask,
+                            const float* u_replace, const float* u_random, const int64_t* random_words, int64_t* out_ids,
+                            int64_t* labels, int64_t* attention_mask, long n, int64_t pad_id, int64_t mask_id,
+                            float mlm_probability, hipStream_t stream);
+int vt_assemble_regions_dispatch(const float* img_feats, const int64_t* region_counts, const int64_t* region_view_ids,
+                                 const int64_t* current_view, const float* loc_table, const int64_t* text_labels,
+                                 const int64_t* text_mask, const int64_t* text_token_classes, float* feats_out, float* loc_out,
+                                 int64_t* labels_out, int64_t* mask_out, int64_t* token_labels_out, int B, int T, int R,
+                                 int R_in, int D, hipStream_t stream);
+
+// ---- fp32_path.hip: the fp32 inference path (and the fp32 training step's GEMM and LayerNorm)
+int vt_gemm_f32_dispatch(const float* A, long lda, long sA_b, long sA_h, const float* W, long ldw, long sW_b, long sW_h,
+                         int w_is_kn, const float* bias, const float* R, long ldr, float* C, long ldc, long sC_b, long sC_h,
+                         int M, int N, int K, int act, float alpha, int batch, int heads, int grp_rows, int grp_stride,
+                         hipStream_t stream);
+int vt_gemm_f32_split_for(int M, int N, int K);
+int vt_gemm_f32_ex_dispatch(const float* A, long lda, long sA_b, long sA_h, int a_is_km, const float* W, long ldw, long sW_b,
+                            long sW_h, int w_is_kn, const float* bias, const float* R, long ldr, float* C, long ldc, long sC_b,
+                            long sC_h, float* pre, int M, int N, int K, int act, float alpha, int batch, int heads,
+                            int grp_rows, int grp_stride, int accumulate, int split, float* ws, DropCfg drop,
+                            hipStream_t stream);
+int vt_softmax_rows_f32_dispatch(float* x, long ld, long rows, int cols, float scale, const float* mask, int mask_mode,
+                                 const float* head_scale, int nh, int S, hipStream_t stream);
+int vt_layernorm_f32_dispatch(const void* x, long ldx, int x_is_f32, void* y, long ldy, int y_is_f32, const float* gamma,
+                              const float* beta, long M, int H, float eps, int grp_rows, int grp_stride, hipStream_t stream);
+int vt_layernorm_f32_drop_dispatch(const void* x, long ldx, int x_is_f32, void* y, long ldy, int y_is_f32, const float* gamma,
+                                   const float* beta, long M, int H, float eps, int grp_rows, int grp_stride, DropCfg drop,
+                                   hipStream_t stream, int drop_entry = 1);
+int vt_embed_layernorm_f32_dispatch(const int64_t* ids, const int64_t* type_ids, const int64_t* pos_ids, const float* word,
+                                    const float* pos, const float* type, const float* gamma, const float* beta, float* y,
+                                    long ldy, int B, int T, int S, int H, int n_word, int n_pos, int n_type, float eps,
+                                    int* err_flag, hipStream_t stream);
+
+// ---- fp32_train.hip: what only the fp32 training step runs
+int vt_colsum_f32_dispatch(const float* x, long ldx, long rows, int cols, float* out, int accumulate, float* ws,
+                           hipStream_t stream);
+int vt_ln_bwd_f32_blocks(long M);
+int vt_ln_bwd_f32_dispatch(const float* x, long ldx, const float* g, long ldg, int grp_rows, int grp_stride, const float* gamma,
+                           float* dx, long lddx, float* dx_drop, long ldd, float* partial, long M, int H, float eps, DropCfg din,
+                           DropCfg dout, hipStream_t stream);
+int vt_attn_softmax_f32_dispatch(int backward, float* x, float* pd, long ld, int B, int nh, int S, float scale, const float* mask,
+                                 int mask_mode, const float* head_scale, DropCfg drop, hipStream_t stream);
+int vt_dgelu_f32_dispatch(const float* g, const float* pre, float* out, long n, hipStream_t stream);
+int vt_embed_sum_f32_dispatch(const int64_t* ids, const int64_t* type_ids, const int64_t* pos_ids, const float* word,
+                              const float* pos, const float* type, float* e, int B, int T, int H, int n_word, int n_pos,
+                              int n_type, int* err, hipStream_t stream);
+int vt_dropout_rows_f32_dispatch(const float* x, long ldx, int grp_rows, int grp_stride, float* y, long ldy, long rows, int cols,
+                                 DropCfg d, hipStream_t stream);
+
+// ---- gemm_bf16.hip: the NT GEMM's host entries and tuning hooks
+void vt_gemm_set_trace(void* p);
+void vt_gemm_set_variant(int v);
+void vt_gemm_tune_set(int M, int N, int K, int kind, int variant);
+int vt_gemm_dispatch(const void* A, long lda, const void* W, long ldw, const float* bias, const void* R, long ldr,
+                     void* C, long ldc, int M, int N, int K, int act, int out_mode, int grp_rows, int grp_stride,
+                     hipStream_t stream, void* C2 = nullptr, long ldc2 = 0, const DropCfg* drop = nullptr,
+                     const VtLnResidual* rln = nullptr);
+int vt_gemm_ln_dispatch(const void* A, long lda, const void* W, long ldw, const float* bias, const float* colv,
+                        const float* stats_in, int np, long stat_rows, float eps, int ln_mode, const void* Rs, long ldrs,
+                        void* C, long ldc, void* Cs, long ldcs, float* stats_out, int M, int N, int K, int act,
+                        hipStream_t stream);
+int vt_gemm_splitk_dispatch(const void* A, long lda, const void* W, long ldw, void* C, long ldc, float* ws, int M, int N, int K,
+                            int ksplit, hipStream_t stream);
+
+// ---- gemm_v7.hip: reserved CUs and the caller-owned GEMM workspace
+void vt_gemm_set_reserved_cus(int k);
+int vt_gemm_set_workspace_impl(void* base, long bytes);
+long vt_gemm_workspace_region_bytes_impl();
+int vt_gemm_shared_tile_timeouts_impl(unsigned* out);
+int vt_gemm_sk_counter_ptrs(unsigned** ptrs, int max);
+
+// ---- gemm_wgrad.hip
+void vt_wgrad_set_tile(int tn);
+int vt_wgrad_dispatch(WgradArgs& a, hipStream_t stream);
+
+// ---- gemm_wgrad_v8.hip: the persistent weight-gradient kernel's switch and timeout counter
+void vt_wgrad_v8_enable(int on);
+int vt_wgrad_v8_timeouts(unsigned* out);
+unsigned* vt_wgrad_timeouts_devptr();
+
+// ---- ln_deferred.hip: the inference path's deferred LayerNorm
+int vt_ln_apply_dispatch(const void* v, long ldv, const float* stats, int np, long stat_rows, const float* gamma,
+                         const float* beta, float eps, void* y16, long ldy16, float* y32, long ldy32, long M, int H,
+                         hipStream_t stream);
+int vt_ln_stream_init_dispatch(const float* x, long ldx, void* s16, long lds, void* y16, long ldy, float* stats, int np,
+                               long stat_rows, long M, int H, float eps, hipStream_t stream);
+
+// ---- lstm_persistent.hip
+long vt_lstm_persistent_ws_bytes(int B, int hs);
+int vt_lstm_persistent_dispatch(LstmPersistArgs a, void* ws, long ws_bytes, hipStream_t stream);
+
+// ---- rollout.hip
+int vt_lstm_step_dispatch(const LstmStepArgs& a, hipStream_t stream);
+int vt_lstm_step_bwd_dispatch(const LstmBwdArgs& a, hipStream_t stream);
+int vt_softdot_dispatch(const SoftDotArgs& a, hipStream_t stream);
+long vt_softdot_bwd_split_ws_floats(int B, int L, int D);
+int vt_softdot_bwd_split_dispatch(const SoftDotBwdArgs& a, float* ws, hipStream_t stream);
+int vt_softdot_bwd_dispatch(const SoftDotBwdArgs& a, hipStream_t stream);
+int vt_skinny_linear_dispatch(const SkinnyArgs& a, hipStream_t stream);
+
+// ---- rowops.hip: LayerNorm, embeddings, losses, optimizer and the other row kernels
+int vt_layernorm_dispatch(const void* x, long ldx, void* y, long ldy, const float* gamma, const float* beta,
+                          float* mean, float* rstd, int M, int H, float eps, int grp_rows, int grp_stride,
+                          hipStream_t stream, int x_f16 = 0, void* y_f16 = nullptr, long ldyh = 0,
+                          const PrefetchArgs* pf = nullptr);
+int vt_embed_layernorm_dispatch(const int64_t* ids, const int64_t* type_ids, const int64_t* pos_ids, const float* word,
+                                const float* pos, const float* type, const float* gamma, const float* beta, void* y,
+                                long ldy, int B, int T, int S, int H, int n_word, int n_pos, int n_type, float eps,
+                                int* err_flag, hipStream_t stream, const DropCfg* drop = nullptr);
+int vt_pack_concat_dispatch(const float* s0, int d0, const float* s1, int d1, void* out, int kpad, long rows,
+                            hipStream_t stream);
+int vt_layernorm_bwd_dispatch(const void* x, long ldx, const void* dy, long ldy, const float* gamma, void* dx, long lddx,
+                              float* dgamma, float* dbeta, float* partial_ws, int M, int H, float eps, int accumulate,
+                              hipStream_t stream, void* dx2 = nullptr, long lddx2 = 0, const DropCfg* drop = nullptr,
+                              int x_f16 = 0, const PrefetchArgs* pf = nullptr);
+int vt_dgelu_mul_dispatch(const void* g, const void* h, void* out, long n, hipStream_t stream);
+int vt_embed_layernorm_bwd_dispatch(const int64_t* ids, const int64_t* type_ids, const int64_t* pos_ids, const float* word,
+                                    const float* pos, const float* type, const float* gamma, const void* g, long ldg,
+                                    float* de, float* dgamma, float* dbeta, float* partial_ws, int B, int T, int S, int H,
+                                    int n_word, int n_pos, int n_type, float eps, int accumulate, hipStream_t stream,
+                                    const DropCfg* drop = nullptr);
+int vt_adamw_dispatch(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16, long n, float lr,
+                      float step_size, float b1, float b2, float eps, float wd, float grad_scale, hipStream_t stream);
+int vt_scale_heads_dispatch(const void* x, long ldx, void* out, long ldo, long rows, int nh, const float* scale, hipStream_t stream);
+int vt_cast_scale_dispatch(const float* x, void* y, long n, float scale, hipStream_t stream);
+int vt_transpose_dispatch(const void* in, long ldi, void* out, long ldo, int R, int C, hipStream_t stream);
+int vt_transpose_batch_dispatch(const void* const* in, const long* ldi, void* const* out, const long* ldo, const int* R,
+                                const int* C, int n, hipStream_t stream);
+int vt_ce_softmax_dispatch2(const float* z, long ldz, const int64_t* y, float* loss_row, int64_t* amax, void* dz, long lddz,
+                            long rows, int V, int Vpad, float scale, int dz_f32, hipStream_t stream);
+int vt_ce_softmax_dispatch(const float* z, long ldz, const int64_t* y, float* loss_row, int64_t* amax, void* dz, long lddz,
+                           long rows, int V, int Vpad, float scale, hipStream_t stream);
+int vt_ce_double_softmax_dispatch2(const float* z, long ldz, const int64_t* y, float* loss_row, int64_t* amax, void* dz, long lddz,
+                                   long rows, int V, int Vpad, float scale, int dz_f32, hipStream_t stream);
+int vt_ce_double_softmax_dispatch(const float* z, long ldz, const int64_t* y, float* loss_row, int64_t* amax, void* dz, long lddz,
+                                  long rows, int V, int Vpad, float scale, hipStream_t stream);
+int vt_apply_dropout_dispatch(void* x, long ld, long rows, int cols, const DropCfg& d, hipStream_t stream);
+int vt_dropout_mask_dispatch(uint8_t* out, long n, const DropCfg& d, hipStream_t stream, int attn);
+int vt_embed_table_grad_dispatch(const int* sorted_ids, const long* perm, const float* de, long ld_de, float* grad, long ld_grad,
+                                 long n, int H, long n_rows_table, long skip_id, float* scratch, int* flag, hipStream_t stream);
+int vt_center_mask_dispatch(const void* mask, int kind, long ldm, float* out, int B, int S, hipStream_t stream);
+int vt_batch_rows_dispatch(const BatchRowsArgs& a, int lists, hipStream_t stream);
+int vt_action_head_dispatch2(const float* z, long ldz, const long* y, int B, int A, float grad_scale, void* dz, long lddz, int Ap,
+                             float* out, int dz_f32, hipStream_t stream);
+int vt_action_head_dispatch(const float* z, long ldz, const long* y, int B, int A, float grad_scale, void* dz, long lddz, int Ap,
+                            float* out, hipStream_t stream);
+int vt_prefetch_dispatch(const void* const* ptrs, const long* bytes, int n, hipStream_t stream);

@@ -18,7 +18,7 @@
 // A-transposed operand (a_is_km) gives the weight gradients dW = dY^T . X and the attention's dK = dS^T . Q / dV = P^T . dC,
 // a fixed-order split of the K range (partial planes, summed in order by gemm_f32_split_reduce) keeps a long token-row
 // reduction on the whole chip, and the epilogue can save the pre-activation, apply a dropout site and accumulate into C.
-#include "common.hpp"
+#include "dispatch.hpp"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
@@ -396,10 +396,6 @@ __global__ __launch_bounds__(256) void layernorm_rows_f32(LnF32Args a) {
     }
   }
 }
-
-int vt_layernorm_f32_drop_dispatch(const void* x, long ldx, int x_is_f32, void* y, long ldy, int y_is_f32, const float* gamma,
-                                   const float* beta, long M, int H, float eps, int grp_rows, int grp_stride, DropCfg drop,
-                                   hipStream_t stream, int drop_entry = 1);
 
 int vt_layernorm_f32_dispatch(const void* x, long ldx, int x_is_f32, void* y, long ldy, int y_is_f32, const float* gamma,
                               const float* beta, long M, int H, float eps, int grp_rows, int grp_stride, hipStream_t stream) {

@@ -14,7 +14,7 @@
 //   dgelu_f32           g * GELU'(pre) of the erf form
 //   embed_sum_f32       word + position + token_type rows (the embedding LayerNorm's input, saved for its backward)
 //   dropout_rows_f32    y = x * keep / (1 - p) with a row remap on the input (the image rows' gradient)
-#include "common.hpp"
+#include "dispatch.hpp"
 
 #define CS_ROWS 256   // rows per partial of colsum_f32: the partial count is a function of the row count only
 

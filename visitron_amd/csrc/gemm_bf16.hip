@@ -27,6 +27,7 @@
 // one-wave-per-SIMD 256x256 kernels with AGPR accumulators are in gemm_v7.hip (variants 15, 16).
 #include <mutex>
 #include "gemm_common.hpp"
+#include "dispatch.hpp"
 
 // ================================================================================================
 // v2: the same tile / fragment / epilogue design with
@@ -693,13 +694,7 @@ __global__ __launch_bounds__(512, 4) void gemm_nt_bf16_v6(GemmArgs g) {
 //          15 / 16 = 256x256 tile, 4 waves of 128x128 with AGPR accumulators, one tile per workgroup / persistent
 //          (gemm_v7.hip); 18 .. 21 = the persistent kernel on 224- / 192- / 160- / 128-row tiles (fewer, better balanced rounds when the
 //          256-row tiling leaves the last round mostly empty).
-int vt_gemm_v7_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stream, int mtn);  // gemm_v7.hip (tile height 32 * mtn)
-int vt_gemm_v8_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stream, int mtn, bool shared_tiles = false);  // gemm_v7.hip (persistent; tile height 32 * mtn)
-#ifdef VT_EXPERIMENTAL_GEMM   // tools/experiments (make gemmlab): the measured-negative redesigns of round 4, variants 24 .. 27; not in the product
-int vt_gemm_v10_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stream);           // gemm_v10.hip (two persistent 256x128-tile workgroups per CU)
-int vt_gemm_v11_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stream);           // gemm_v11.hip (eight waves on shared 256x256 stages)
-int vt_gemm_v12_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stream, int mtn);  // gemm_v12.hip (short tiles on three operand stages)
-#endif
+//          24 .. 27 (VT_EXPERIMENTAL_GEMM only) = the measured-negative redesigns of round 4, tools/experiments.
 static void* g_gemm_trace = nullptr;
 void vt_gemm_set_trace(void* p) { g_gemm_trace = p; }
 static int g_gemm_variant = -1;  // -1: table / heuristic (tuning hook only; set through vt_debug_set_gemm_variant)
@@ -803,7 +798,6 @@ static int launch_kernel(K kern, const GemmArgs& g, int lds_bytes, hipStream_t s
 // kernel sums a tile's copies IN ORDER (deterministic) and runs the ordinary register epilogue -- bias, activation, dropout,
 // residual / rebuilt-LayerNorm residual, second output, fp16 / bf16 / fp32 store, row remap -- on the sums (epi_row_direct, the
 // code the register-epilogue kernels run: every epilogue kind is served).  The autotuner decides per (M, N, K, kind).
-int vt_gemm_splitk_tiles_launch(const GemmArgs& g, int act, int out_f32, int ks, hipStream_t stream);   // gemm_v7.hip
 template <int ACT, bool OUT_F32>
 static int launch_splitk_epi(const GemmArgs& g, hipStream_t stream) {
   const int cus = vt_device_cus();
@@ -874,8 +868,7 @@ static int launch_gemm(const GemmArgs& g, int variant, hipStream_t stream) {
 // Host entry used by the C ABI (capi.hip).  Returns a VT_* code; never synchronises.
 int vt_gemm_dispatch(const void* A, long lda, const void* W, long ldw, const float* bias, const void* R, long ldr,
                      void* C, long ldc, int M, int N, int K, int act, int out_mode, int grp_rows, int grp_stride,
-                     hipStream_t stream, void* C2 = nullptr, long ldc2 = 0, const DropCfg* drop = nullptr,
-                     const VtLnResidual* rln = nullptr) {
+                     hipStream_t stream, void* C2, long ldc2, const DropCfg* drop, const VtLnResidual* rln) {
   // out_mode: bit 0 fp32 output; bit 1 C written as fp16 (saturating) instead of bf16; bit 2 the residual R holds fp16
   // (GemmArgs::c_f16 / r_f16: the training layer's higher-precision residual stream)
   const int out_f32 = out_mode & 1, c_f16 = (out_mode >> 1) & 1, r_f16 = (out_mode >> 2) & 1;
@@ -958,7 +951,6 @@ int vt_gemm_dispatch(const void* A, long lda, const void* W, long ldw, const flo
 }
 
 // ---- deferred-LayerNorm GEMMs (GemmArgs::ln_mode; gemm_v7_ln.hip) --------------------------------------------------
-int vt_gemm_ln_launch(const GemmArgs& g, int act, int variant, hipStream_t stream);
 // mode 1: C = act(rstd_r (A W^T - mean_r colv) + bias), statistics of A's rows (row length K) from stats_in;
 // mode 2: v = A W^T + bias + colv * ((Rs - mean_r) rstd_r) (row length N) -> Cs (fp16), C (bf16), stats_out.
 int vt_gemm_ln_dispatch(const void* A, long lda, const void* W, long ldw, const float* bias, const float* colv,
@@ -992,8 +984,6 @@ int vt_gemm_ln_dispatch(const void* A, long lda, const void* W, long ldw, const 
 // ---- split-K: C[M,N] (bf16) = A[M,K] W[N,K]^T for a long K and few output tiles --------------------------------------
 // ksplit copies of the 256x256 tile list of the one-tile-per-workgroup kernel, each over its share of the K-steps, write fp32
 // planes into `ws` (ksplit * M * N floats); splitk_reduce_bf16 sums them.  No bias / activation / residual.
-int vt_gemm_v7_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stream, int mtn);
-
 __global__ __launch_bounds__(256) void splitk_reduce_bf16(const float* __restrict__ ws, long plane, int ksplit, bf16_t* __restrict__ C,
                                                           long ldc, long M, int N) {
   const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;   // element index in [M, N] (N % 4 == 0)

@@ -83,6 +83,21 @@ enum { ACT_NONE = 0, ACT_GELU = 1, ACT_TANH = 2, ACT_MUL = 3 };  // MUL: out = a
 #define GEMM_LDS_BYTES (4 * GEMM_TILE_BYTES)
 #define GEMM_DEFAULT_VARIANT 1
 
+// ---- launchers that cross a translation unit (called from vt_gemm_dispatch / vt_gemm_ln_dispatch, gemm_bf16.hip) ----------
+// gemm_v7.hip: 256x256-tile kernels, tile height 32 * mtn; v8 is the persistent form (sk: with the stream-K region)
+int vt_gemm_v7_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stream, int mtn);
+int vt_gemm_v8_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stream, int mtn, bool sk = false);
+int vt_gemm_splitk_tiles_launch(const GemmArgs& g, int act, int out_f32, int ks, hipStream_t stream);
+int vt_gemm_persistent_cus();               // the device's CU count less the reserved ones (vt_gemm_reserve_cus)
+int vt_gemm_v8_take_region(GemmArgs& g);    // shared-tile workspace of this launch (0: none registered)
+// gemm_v7_ln.hip: the deferred-LayerNorm epilogues (GemmArgs::ln_mode)
+int vt_gemm_ln_launch(const GemmArgs& g, int act, int variant, hipStream_t stream);
+#ifdef VT_EXPERIMENTAL_GEMM   // tools/experiments (make gemmlab): the measured-negative redesigns of round 4, variants 24 .. 27; not in the product
+int vt_gemm_v10_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stream);           // gemm_v10.hip (two persistent 256x128-tile workgroups per CU)
+int vt_gemm_v11_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stream);           // gemm_v11.hip (eight waves on shared 256x256 stages)
+int vt_gemm_v12_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stream, int mtn);  // gemm_v12.hip (short tiles on three operand stages)
+#endif
+
 template <int ACT>
 __device__ __forceinline__ float apply_act(float x) {
   if (ACT == ACT_GELU) return gelu_erf(x);

@@ -3,6 +3,7 @@
 #include <atomic>
 #include <cstdlib>
 #include "gemm_v7_kernels.hpp"
+#include "dispatch.hpp"
 
 // Compute units the persistent grid leaves free (vt_gemm_reserve_cus): with a collective running beside the backward (one
 // process per GPU, RCCL kernels on a few CUs) a persistent workgroup mapped onto a busy CU would stall its share of the

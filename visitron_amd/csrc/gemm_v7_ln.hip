@@ -3,9 +3,6 @@
 // its own so that it compiles beside gemm_v7.hip.
 #include "gemm_v7_kernels.hpp"
 
-int vt_gemm_persistent_cus();   // gemm_v7.hip: the device's CU count less the reserved ones
-int vt_gemm_v8_take_region(GemmArgs& g);   // gemm_v7.hip: shared-tile workspace of this launch (0: none registered)
-
 template <int ACT, int LNM>
 static int launch_ln(const GemmArgs& g, int persistent, int mtn, hipStream_t stream, bool shared_tiles) {
   GemmArgs ga = g;

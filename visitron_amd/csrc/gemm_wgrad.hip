@@ -17,9 +17,7 @@
 // the chip is filled in a single round.  MFMA operands are arranged (A = X^T, B = dY^T) so that a
 // lane ends up with 4 consecutive k of one n: 16-byte fp32 stores.  Bias gradients ride along as
 // an extra MFMA against an all-ones A fragment in the k-tile-0 workgroups.
-#include "common.hpp"
-
-#include "wgrad_common.hpp"
+#include "dispatch.hpp"
 
 #define WG_TILE_BYTES (64 * 256)   // X tile: 64 rows x 128 columns
 // TN = width of the dY tile (n-range of the output tile): 128 (4 waves) or 256 (8 waves, 85 instead of 64
@@ -227,8 +225,6 @@ static int wgrad_launch(WgradArgs& a, int total, hipStream_t stream) {
   }
   return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
 }
-
-int vt_wgrad_v8_dispatch(WgradArgs& a, hipStream_t stream, bool force);   // gemm_wgrad_v8.hip
 
 int vt_wgrad_dispatch(WgradArgs& a, hipStream_t stream) {
   if (a.nprob <= 0 || a.nprob > WG_MAX_PROBLEMS || a.M <= 0) return VT_ERR_BAD_SHAPE;

@@ -6,7 +6,7 @@
 //   ln_stream_init  layer-0 input: the embedding output x0 (fp32) -> the stream (fp16), its bf16 copy and the identity
 //                   statistics (mean 0, rstd 1: x0 is not normalised again), so that the first layer runs the same kernels
 //                   as the others.
-#include "common.hpp"
+#include "dispatch.hpp"
 
 struct LnApplyArgs {
   const uint16_t* v; long ldv;   // fp16 rows

@@ -18,20 +18,7 @@
 // have finished READING the buffer step i+1 overwrites.  The arithmetic is the step kernel's: the fp32 state is rounded
 // to bf16 for the recurrent product (here when it is published instead of when it is loaded: same values), gates and
 // state update in fp32, packed-sequence rule (a row past its length keeps its state, its output position is zero).
-#include "common.hpp"
-#include "rollout_args.hpp"
-
-struct LstmPersistArgs {
-  const float* xproj; long ldx_b, ldx_t;   // padded layout: row (b, t) at xproj + b * ldx_b + t * ldx_t (xrow_start == null)
-  const int* xrow_start;                   // compacted layout: row (b, t) at xproj + (xrow_start[b] + t) * ldx_t
-  float* h; float* c;                      // [B, hs] fp32: initial state in, final state out
-  const bf16_t* w_hh;                      // [4 hs, hs]
-  const int* lengths;                      // [B] or null
-  float* seq_out; long lds_b, lds_t;       // optional [B, T, hs] view
-  bf16_t* xchg;                            // 2 x [hs / 16][Bp][16] bf16 exchange buffers (Bp = batch rounded up to 16)
-  unsigned* sync;                          // [0] arrival counter, [1] timeout flag (zeroed by the launcher)
-  int B, hs, T, reverse;
-};
+#include "dispatch.hpp"
 
 __device__ __forceinline__ float lp_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ __forceinline__ float lp_tanh(float x) {

@@ -5,8 +5,7 @@
 // The dense projections of these modules go through the NT GEMM (gemm_bf16.hip); what is here is the part with no
 // GEMM shape: the recurrent product h . W_hh^T fused with the gate arithmetic, and the batched dot / softmax / weighted
 // sum over a short context.
-#include "common.hpp"
-#include "rollout_args.hpp"
+#include "dispatch.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // One LSTM time step (torch.nn.LSTM / LSTMCell semantics, gate order i, f, g, o):

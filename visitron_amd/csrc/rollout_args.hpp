@@ -1,4 +1,4 @@
-// Argument blocks of the rollout kernels (rollout.hip), shared with the C-ABI layer (capi.hip).
+// Argument blocks of the rollout kernels (rollout.hip, lstm_persistent.hip), shared with the C-ABI layer (capi.hip).
 #pragma once
 #include "common.hpp"
 
@@ -63,4 +63,17 @@ struct SkinnyArgs {
   const float* bias;                   // [N] or null
   float* out; long ldo;                // [M, N] fp32
   int M, N, Kpad, act;                 // act: 0 none, 2 tanh
+};
+
+// The whole recurrence as one persistent launch (lstm_persistent.hip).
+struct LstmPersistArgs {
+  const float* xproj; long ldx_b, ldx_t;   // padded layout: row (b, t) at xproj + b * ldx_b + t * ldx_t (xrow_start == null)
+  const int* xrow_start;                   // compacted layout: row (b, t) at xproj + (xrow_start[b] + t) * ldx_t
+  float* h; float* c;                      // [B, hs] fp32: initial state in, final state out
+  const bf16_t* w_hh;                      // [4 hs, hs]
+  const int* lengths;                      // [B] or null
+  float* seq_out; long lds_b, lds_t;       // optional [B, T, hs] view
+  bf16_t* xchg;                            // 2 x [hs / 16][Bp][16] bf16 exchange buffers (Bp = batch rounded up to 16)
+  unsigned* sync;                          // [0] arrival counter, [1] timeout flag (zeroed by the launcher)
+  int B, hs, T, reverse;
 };

@@ -9,7 +9,7 @@
 //                       sequence buffer directly (no torch.cat, :287).
 //   pack_region_inputs  [img_feats | img_location_embeddings | 0-pad] fp32 -> bf16 K-concatenated GEMM
 //                       operand, so img_embedding + location_embeds (encoder.py:277-279) is ONE GEMM.
-#include "common.hpp"
+#include "dispatch.hpp"
 
 __global__ void prefetch_ranges(PrefetchArgs a);   // (defined at the end of this file)
 
@@ -244,8 +244,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_full(LnArgs a) {
 
 int vt_layernorm_dispatch(const void* x, long ldx, void* y, long ldy, const float* gamma, const float* beta,
                           float* mean, float* rstd, int M, int H, float eps, int grp_rows, int grp_stride,
-                          hipStream_t stream, int x_f16 = 0, void* y_f16 = nullptr, long ldyh = 0,
-                          const PrefetchArgs* pf = nullptr) {
+                          hipStream_t stream, int x_f16, void* y_f16, long ldyh, const PrefetchArgs* pf) {
   if (!x || !y || !gamma || !beta) return VT_ERR_NULL;
   if (M <= 0 || H <= 0 || (H % 8) || H > 64 * 8 * 4) return VT_ERR_BAD_SHAPE;
   if ((ldx % 8) || (ldy % 8) || (((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) & 15)) return VT_ERR_BAD_ALIGN;
@@ -390,7 +389,7 @@ __global__ __launch_bounds__(256) void embed_layernorm(EmbArgs a) {
 int vt_embed_layernorm_dispatch(const int64_t* ids, const int64_t* type_ids, const int64_t* pos_ids, const float* word,
                                 const float* pos, const float* type, const float* gamma, const float* beta, void* y,
                                 long ldy, int B, int T, int S, int H, int n_word, int n_pos, int n_type, float eps,
-                                int* err_flag, hipStream_t stream, const DropCfg* drop = nullptr) {
+                                int* err_flag, hipStream_t stream, const DropCfg* drop) {
   if (!ids || !word || !pos || !type || !gamma || !beta || !y) return VT_ERR_NULL;
   if (B <= 0 || T <= 0 || S < T || H <= 0 || (H % 8) || H > 2048) return VT_ERR_BAD_SHAPE;
   if ((ldy % 8) || (((uintptr_t)word | (uintptr_t)pos | (uintptr_t)type | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)y) & 15))
@@ -794,8 +793,8 @@ __global__ __launch_bounds__(256) void ln_bwd_reduce(const float* __restrict__ p
 #define LN_BWD_MAX_BLOCKS 1024
 int vt_layernorm_bwd_dispatch(const void* x, long ldx, const void* dy, long ldy, const float* gamma, void* dx, long lddx,
                               float* dgamma, float* dbeta, float* partial_ws, int M, int H, float eps, int accumulate,
-                              hipStream_t stream, void* dx2 = nullptr, long lddx2 = 0, const DropCfg* drop = nullptr,
-                              int x_f16 = 0, const PrefetchArgs* pf = nullptr) {
+                              hipStream_t stream, void* dx2, long lddx2, const DropCfg* drop, int x_f16,
+                              const PrefetchArgs* pf) {
   if (!x || !dy || !gamma || !dx || !dgamma || !dbeta || !partial_ws) return VT_ERR_NULL;
   if (M <= 0 || H <= 0 || (H % 8) || H > 1024) return VT_ERR_BAD_SHAPE;
   if ((ldx % 8) || (ldy % 8) || (lddx % 8) || (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15)) return VT_ERR_BAD_ALIGN;
@@ -1013,7 +1012,7 @@ int vt_embed_layernorm_bwd_dispatch(const int64_t* ids, const int64_t* type_ids,
                                     const float* pos, const float* type, const float* gamma, const void* g, long ldg,
                                     float* de, float* dgamma, float* dbeta, float* partial_ws, int B, int T, int S, int H,
                                     int n_word, int n_pos, int n_type, float eps, int accumulate, hipStream_t stream,
-                                    const DropCfg* drop = nullptr) {
+                                    const DropCfg* drop) {
   if (!ids || !word || !pos || !type || !gamma || !g || !de || !dgamma || !dbeta || !partial_ws) return VT_ERR_NULL;
   if (B <= 0 || T <= 0 || S < T || H <= 0 || (H % 8) || H > 1024) return VT_ERR_BAD_SHAPE;
   if ((ldg % 8) || (((uintptr_t)word | (uintptr_t)pos | (uintptr_t)type | (uintptr_t)g | (uintptr_t)de) & 15)) return VT_ERR_BAD_ALIGN;
@@ -1807,19 +1806,6 @@ int vt_center_mask_dispatch(const void* mask, int kind, long ldm, float* out, in
 // mask, every [CLS] and every supervised position kept) and the embedding kernel's out-of-range flag -- into five words the
 // host reads back in one synchronisation; batch_row_lists then writes the row lists (ascending), the padded -> compact
 // map and the per-sequence start / length.  Three short launches where torch needed ~25 (sum, any, nonzero, cumsum, where ...).
-struct BatchRowsArgs {
-  const long* lab; const long* tl;      // [M] or null
-  const float* mask;                    // [B*S] fp32 or null (no compaction wanted)
-  const int* err;                       // the embedding kernel's flag or null
-  long M; int S; int B;
-  long* counts;                         // [5]: err, n_w, n_t, n_keep, bad   (zeroed by the caller)
-  int* tile_counts;                     // [ntiles][3]: per 1024-position tile (written by the counts kernel, read by the lists kernel)
-  long* idx_w; long* idx_t;             // row lists
-  long* index; long* inverse;           // kept rows; padded position -> compact row or -1
-  int* start; int* length;              // [B]
-  long n_w, n_t, n_keep;                // capacities of the three lists (the counts batch_row_counts reported)
-};
-
 // one workgroup per tile of 1024 positions (one position per thread: coalesced)
 __global__ __launch_bounds__(1024) void batch_row_counts(BatchRowsArgs a) {
   __shared__ int red[16][4];

@@ -21,3 +21,5 @@ struct WgradArgs {
   int M;
 };
 
+int vt_wgrad_v8_dispatch(WgradArgs& a, hipStream_t stream, bool force);   // gemm_wgrad_v8.hip, called from vt_wgrad_dispatch
+
