@@ -297,7 +297,7 @@ def test_shared_tiles_in_the_deferred_layernorm_gemms(dev, variant):
     a2 = _rand((M, I), g).to(BF16).to(dev)
     w2 = _rand((H, I), g, 0.03).to(BF16).to(dev)
     b2, c2 = _rand((H,), g, 0.1).to(dev), (1 + 0.1 * _rand((H,), g)).to(dev)
-    plain = 16 if variant == 28 else variant - 11
+    plain = ops.GEMM_VARIANTS[variant]["twin"]
     res = {}
     for v in (plain, variant):
         ops.set_gemm_variant(v)

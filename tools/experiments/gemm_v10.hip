@@ -215,14 +215,5 @@ static int launch_v10(const GemmArgs& g, hipStream_t stream) {
 }
 
 int vt_gemm_v10_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stream) {
-  switch (act * 2 + (out_f32 ? 1 : 0)) {
-    case 0: return launch_v10<ACT_NONE, false>(g, stream);
-    case 1: return launch_v10<ACT_NONE, true>(g, stream);
-    case 2: return launch_v10<ACT_GELU, false>(g, stream);
-    case 3: return launch_v10<ACT_GELU, true>(g, stream);
-    case 4: return launch_v10<ACT_TANH, false>(g, stream);
-    case 5: return launch_v10<ACT_TANH, true>(g, stream);
-    case 6: return launch_v10<ACT_MUL, false>(g, stream);
-    default: return VT_ERR_UNSUPPORTED;
-  }
+  return with_act_out<false>(act, out_f32, [&](auto A, auto O) { return launch_v10<decltype(A)::value, decltype(O)::value>(g, stream); });
 }

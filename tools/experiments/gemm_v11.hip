@@ -259,7 +259,7 @@ static int launch_v11(const GemmArgs& g, hipStream_t stream) {
 // bf16 output in whole 64-column slabs without row remap only (the encoder's shapes); everything else goes to variant 16
 int vt_gemm_v11_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stream) {
   const bool fast = !out_f32 && (g.N & 63) == 0 && g.grp_rows == 0 && act != ACT_TANH;
-  if ((g.K & 63) || 256L * g.lda * 2 + 2L * g.K >= (1L << 31) || 256L * g.ldw * 2 + 2L * g.K >= (1L << 31)) return VT_ERR_UNSUPPORTED;
+  if (!v7_operands_fit(g)) return VT_ERR_UNSUPPORTED;
   if (!fast) return vt_gemm_v8_launch(g, act, out_f32, stream, 8);
   switch (act) {
     case ACT_NONE: return launch_v11<ACT_NONE>(g, stream);

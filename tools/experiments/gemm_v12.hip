@@ -210,7 +210,7 @@ static int launch_v12(const GemmArgs& g, hipStream_t stream) {
 
 int vt_gemm_v12_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stream, int mtn) {
   const bool fast = !out_f32 && (g.N & 63) == 0 && g.grp_rows == 0 && act != ACT_TANH;
-  if ((g.K & 63) || 256L * g.lda * 2 + 2L * g.K >= (1L << 31) || 256L * g.ldw * 2 + 2L * g.K >= (1L << 31)) return VT_ERR_UNSUPPORTED;
+  if (!v7_operands_fit(g)) return VT_ERR_UNSUPPORTED;
   // (odd MTN: the X pieces' swizzle is taken from one per-lane offset by an xor, which needs the row pitch to be a multiple of 128 B)
   if (!fast || (mtn != 4 && (g.lda & 63))) return vt_gemm_v8_launch(g, act, out_f32, stream, mtn);
   switch (act * 2 + (mtn == 4 ? 1 : 0)) {

@@ -272,7 +272,6 @@ int main(int argc, char** argv) {
   lab_fill<<<1024, 256>>>(A, (long)M * K, 1u);
   lab_fill<<<1024, 256>>>(W, (long)N * K, 2u);
   GemmArgs g;
-  memset(&g, 0, sizeof(g));
   g.A = A; g.W = W; g.C = C; g.lda = K; g.ldw = K; g.ldc = N; g.M = M; g.N = N; g.K = K;
   g.tiles_m = (M + 255) / 256; g.tiles_n = (N + 255) / 256;
   auto kern = gemm_nt_bf16_v8<ACT_NONE, false, true, false, 8, 0>;

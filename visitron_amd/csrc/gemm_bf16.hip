@@ -24,7 +24,7 @@
 //   * block ids are remapped so that the tiles sharing an activation row-panel run on one XCD
 //     (one L2).
 // This file holds the 2-waves-per-SIMD kernels (v2, v4, v5, v6 below) and the dispatcher / shape table; the
-// one-wave-per-SIMD 256x256 kernels with AGPR accumulators are in gemm_v7.hip (variants 15, 16).
+// one-wave-per-SIMD 256x256 kernels with AGPR accumulators are in gemm_v7.hip.  gemm_variants.def lists every variant.
 #include <mutex>
 #include "gemm_common.hpp"
 #include "dispatch.hpp"
@@ -689,12 +689,6 @@ __global__ __launch_bounds__(512, 4) void gemm_nt_bf16_v6(GemmArgs g) {
 }
 
 // ---- launchers ---------------------------------------------------------------------------------
-// variant: 1 = 128x128 tile, 4 waves, BK 64, 2-stage ring (v2); 14 = the same tile with 8 waves of 32x64 (v6);
-//          9 / 10 = 256x192 / 256x256 tile, 8 waves (v4); 11 = 256x256, BK 32, 4-stage ring, phased (v5);
-//          15 / 16 = 256x256 tile, 4 waves of 128x128 with AGPR accumulators, one tile per workgroup / persistent
-//          (gemm_v7.hip); 18 .. 21 = the persistent kernel on 224- / 192- / 160- / 128-row tiles (fewer, better balanced rounds when the
-//          256-row tiling leaves the last round mostly empty).
-//          24 .. 27 (VT_EXPERIMENTAL_GEMM only) = the measured-negative redesigns of round 4, tools/experiments.
 static void* g_gemm_trace = nullptr;
 void vt_gemm_set_trace(void* p) { g_gemm_trace = p; }
 static int g_gemm_variant = -1;  // -1: table / heuristic (tuning hook only; set through vt_debug_set_gemm_variant)
@@ -790,7 +784,7 @@ static int launch_kernel(K kern, const GemmArgs& g, int lds_bytes, hipStream_t s
   return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
 }
 
-// ---- variant 33: split-K with the WHOLE epilogue behind the reduction (round 6) ----------------------------------------
+// ---- family SPLITK_EPI: split-K with the WHOLE epilogue behind the reduction (round 6) ------------------------------------
 // Small batches leave a long-K product a handful of 256x256 tiles, each a chain of K / 64 dependent K-steps of ~0.8 us whatever
 // M is (the reference's own batch sizes: 2 x 767 or 8 x 511 rows per GPU; [912, 768] x 3 072 takes 38 us for 3.6 GFLOP).
 // ksplit copies of the tile list of the one-tile-per-workgroup kernel each take a share of the K-steps and leave their
@@ -817,49 +811,25 @@ static int launch_splitk_epi(const GemmArgs& g, hipStream_t stream) {
 
 template <int ACT, bool OUT_F32>
 static int launch_gemm(const GemmArgs& g, int variant, hipStream_t stream) {
-  switch (variant) {
-    case 1: return launch_kernel(gemm_nt_bf16_v2<64, 2, ACT, OUT_F32>, g, 2 * 32768, stream);
-    // 35: the same 128x128-tile kernel on a ring of THREE stages (96 KiB: one workgroup per CU).  For launches of fewer tiles
-    // than CUs, where a tile's K-steps are a chain paced by the load latency and two stages keep ONE K-tile in flight: the
-    // long-K products of small batches (round 6; four stages measured no better than three)
-    case 35: return launch_kernel(gemm_nt_bf16_v2<64, 3, ACT, OUT_F32>, g, 3 * 32768, stream);
-    case 9: return launch_kernel_v4(gemm_nt_bf16_v4<192, ACT, OUT_F32>, g, 192, stream);
-    case 10: return launch_kernel_v4(gemm_nt_bf16_v4<256, ACT, OUT_F32>, g, 256, stream);
-    case 11: {
-      GemmArgs g5 = g;
-      g5.tiles_m = (g.M + 255) / 256;
-      g5.tiles_n = (g.N + 255) / 256;
-      auto kern = gemm_nt_bf16_v5<ACT, OUT_F32>;
-      if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768) != hipSuccess) return VT_ERR_HIP;
-      hipLaunchKernelGGL(kern, dim3(g5.tiles_m * g5.tiles_n), dim3(512), 4 * 32768, stream, g5);
+  const gv::Variant* v = gv::find(variant);
+  if (!v) return VT_ERR_UNSUPPORTED;
+  switch (v->family) {
+    case gv::V2_RING2: return launch_kernel(gemm_nt_bf16_v2<64, 2, ACT, OUT_F32>, g, 2 * 32768, stream);
+    case gv::V2_RING3: return launch_kernel(gemm_nt_bf16_v2<64, 3, ACT, OUT_F32>, g, 3 * 32768, stream);
+    case gv::V4_192: return launch_kernel_v4(gemm_nt_bf16_v4<192, ACT, OUT_F32>, g, 192, stream);
+    case gv::V4_256: return launch_kernel_v4(gemm_nt_bf16_v4<256, ACT, OUT_F32>, g, 256, stream);
+    case gv::V5: return launch_kernel_v4(gemm_nt_bf16_v5<ACT, OUT_F32>, g, 256, stream);   // (the launch shape of V4_256: 512 threads, 128 KiB)
+    case gv::V6:
+      hipLaunchKernelGGL((gemm_nt_bf16_v6<ACT, OUT_F32>), dim3(g.tiles_m * g.tiles_n), dim3(512), 2 * 32768, stream, g);
       return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
-    }
-    case 14: {
-      auto kern = gemm_nt_bf16_v6<ACT, OUT_F32>;
-      hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n), dim3(512), 2 * 32768, stream, g);
-      return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
-    }
-    case 15: return vt_gemm_v7_launch(g, ACT, OUT_F32 ? 1 : 0, stream, 8);
-    case 22: return vt_gemm_v7_launch(g, ACT, OUT_F32 ? 1 : 0, stream, 7);   // one tile per workgroup, 224-row tiles
-    case 23: return vt_gemm_v7_launch(g, ACT, OUT_F32 ? 1 : 0, stream, 6);   // ... 192-row tiles (mid-size batches: one fuller round)
-    case 16: return vt_gemm_v8_launch(g, ACT, OUT_F32 ? 1 : 0, stream, 8);
-    case 18: return vt_gemm_v8_launch(g, ACT, OUT_F32 ? 1 : 0, stream, 7);   // the persistent kernel on 224-row tiles
-    case 19: return vt_gemm_v8_launch(g, ACT, OUT_F32 ? 1 : 0, stream, 6);   // ... on 192-row tiles
-    case 20: return vt_gemm_v8_launch(g, ACT, OUT_F32 ? 1 : 0, stream, 5);   // ... on 160-row tiles
-    case 21: return vt_gemm_v8_launch(g, ACT, OUT_F32 ? 1 : 0, stream, 4);   // ... on 128-row tiles (small batches)
-    // 28 .. 32: the persistent kernel (256 .. 128-row tiles) with its left-over tiles SHARED along K among the workgroups a
-    // last round would leave idle (GemmArgs::sk_parts; needs vt_gemm_set_workspace)
-    case 33: return launch_splitk_epi<ACT, OUT_F32>(g, stream);
-    case 28: return vt_gemm_v8_launch(g, ACT, OUT_F32 ? 1 : 0, stream, 8, true);
-    case 29: return vt_gemm_v8_launch(g, ACT, OUT_F32 ? 1 : 0, stream, 7, true);
-    case 30: return vt_gemm_v8_launch(g, ACT, OUT_F32 ? 1 : 0, stream, 6, true);
-    case 31: return vt_gemm_v8_launch(g, ACT, OUT_F32 ? 1 : 0, stream, 5, true);
-    case 32: return vt_gemm_v8_launch(g, ACT, OUT_F32 ? 1 : 0, stream, 4, true);
+    case gv::V7: return vt_gemm_v7_launch(g, ACT, OUT_F32 ? 1 : 0, stream, v->mtn);
+    case gv::V8:
+    case gv::V8_SHARED: return vt_gemm_v8_launch(g, ACT, OUT_F32 ? 1 : 0, stream, v->mtn, v->family == gv::V8_SHARED);
+    case gv::SPLITK_EPI: return launch_splitk_epi<ACT, OUT_F32>(g, stream);
 #ifdef VT_EXPERIMENTAL_GEMM
-    case 24: return vt_gemm_v10_launch(g, ACT, OUT_F32 ? 1 : 0, stream);     // two co-resident persistent workgroups per CU, 256x128 tiles
-    case 25: return vt_gemm_v11_launch(g, ACT, OUT_F32 ? 1 : 0, stream);     // eight waves (two groups of four) on shared 256x256 stages
-    case 26: return vt_gemm_v12_launch(g, ACT, OUT_F32 ? 1 : 0, stream, 5);  // persistent, 160-row tiles on three operand stages
-    case 27: return vt_gemm_v12_launch(g, ACT, OUT_F32 ? 1 : 0, stream, 4);  // ... 128-row tiles
+    case gv::V10: return vt_gemm_v10_launch(g, ACT, OUT_F32 ? 1 : 0, stream);
+    case gv::V11: return vt_gemm_v11_launch(g, ACT, OUT_F32 ? 1 : 0, stream);
+    case gv::V12: return vt_gemm_v12_launch(g, ACT, OUT_F32 ? 1 : 0, stream, v->mtn);
 #endif
     default: return VT_ERR_UNSUPPORTED;
   }
@@ -884,10 +854,8 @@ int vt_gemm_dispatch(const void* A, long lda, const void* W, long ldw, const flo
   g.lda = lda; g.ldw = ldw; g.ldr = ldr; g.ldc = ldc; g.C2 = (bf16_t*)C2; g.ldc2 = ldc2;
   g.M = M; g.N = N; g.K = K;
   g.grp_rows = grp_rows; g.grp_stride = grp_stride;
-  if (drop) g.drop = *drop; else { g.drop.thresh = 0; g.drop.seed = 0; g.drop.scale = 1.0f; }
+  if (drop) g.drop = *drop;
   g.trace = (unsigned long long*)g_gemm_trace;
-  g.ln_mode = 0; g.ln_np = 0; g.ln_rows = 0; g.ln_inv_n = 0.f; g.ln_eps = 0.f; g.ln_stats = nullptr; g.colv = nullptr;
-  g.Rs = nullptr; g.Cs = nullptr; g.stats_out = nullptr; g.ldrs = 0; g.ldcs = 0; g.ksplit = 0; g.reverse = 0; g.c_plane = 0;
   g.r_f16 = r_f16; g.c_f16 = c_f16;
   if (rln) {   // residual = LayerNorm(R) from saved row statistics (GemmArgs::r_mean)
     if (!rln->mean || !rln->rstd || !rln->gamma || !rln->beta) return VT_ERR_NULL;
@@ -900,25 +868,16 @@ int vt_gemm_dispatch(const void* A, long lda, const void* W, long ldw, const flo
   g.tiles_n = (N + GEMM_BN - 1) / GEMM_BN;
   int variant = g_gemm_variant >= 0 ? g_gemm_variant
                                     : vt_gemm_pick_variant(M, N, K, VT_TUNE_KIND(act, R != nullptr, C2 != nullptr, out_f32 != 0, 0));
-  if ((r_f16 || c_f16) && (variant == 9 || variant == 10)) variant = 1;   // the 256 x 192 / 256 kernels' grouped epilogue reads / writes bf16 only
-  auto launch = [&](const GemmArgs& ga, int v) {
-    switch (act * 2 + (out_f32 ? 1 : 0)) {
-      case 0: return launch_gemm<ACT_NONE, false>(ga, v, stream);
-      case 1: return launch_gemm<ACT_NONE, true>(ga, v, stream);
-      case 2: return launch_gemm<ACT_GELU, false>(ga, v, stream);
-      case 3: return launch_gemm<ACT_GELU, true>(ga, v, stream);
-      case 4: return launch_gemm<ACT_TANH, false>(ga, v, stream);
-      case 5: return launch_gemm<ACT_TANH, true>(ga, v, stream);
-      case 6: return launch_gemm<ACT_MUL, false>(ga, v, stream);
-      default: return VT_ERR_UNSUPPORTED;
-    }
+  if ((r_f16 || c_f16) && (gv::flags(variant) & gv::BF16_IO_ONLY)) variant = GEMM_DEFAULT_VARIANT;   // the grouped epilogue reads / writes bf16 only
+  auto launch = [&](const GemmArgs& ga, int v) {   // (ACT_MUL with fp32 output: refused, not instantiated)
+    return with_act_out<false>(act, out_f32, [&](auto A, auto O) { return launch_gemm<decltype(A)::value, decltype(O)::value>(ga, v, stream); });
   };
   // Tail rows of the persistent kernel.  T = 256x256 tiles over `cus` CUs: F full rounds and a last round with R tiles.
   // When that last round is at most half full, its rows go to the 128x128-tile kernel instead (two workgroups per
   // CU: R * 4 <= 2 * cus small tiles = one round of 0.58 of the big tile's time); the persistent kernel keeps the rows
   // of the F full rounds.  Dropout: element index = m * N + n and the hash is linear in (index/2 + seed), so the row
   // offset of the second launch is a seed offset.  Not when a variant is forced (tuning) or rows are remapped.
-  if (variant == 16 && g_gemm_variant < 0 && g_gemm_tail_split && grp_rows == 0 && (N & 1) == 0) {
+  if (variant == GEMM_PERSISTENT_VARIANT && g_gemm_variant < 0 && g_gemm_tail_split && grp_rows == 0 && (N & 1) == 0) {
     const int cus = vt_device_cus();
     const long tn = (N + 255) / 256, tm = (M + 255) / 256, T = tm * tn;
     if (cus > 0 && T > cus) {
@@ -937,16 +896,16 @@ int vt_gemm_dispatch(const void* A, long lda, const void* W, long ldw, const flo
         g2.C = out_f32 ? (void*)((float*)C + M1 * ldc) : (void*)((bf16_t*)C + M1 * ldc);
         if (g.C2) g2.C2 = g.C2 + M1 * ldc2;
         g2.drop.seed = g.drop.seed + (uint32_t)((M1 * N) >> 1);
-        const int rc = launch(g1, 16);
+        const int rc = launch(g1, GEMM_PERSISTENT_VARIANT);
         if (rc) return rc;
-        return launch(g2, 1);
+        return launch(g2, GEMM_DEFAULT_VARIANT);
       }
     }
   }
   const int rc = launch(g, variant);
   // a table entry tuned at a neighbouring row count may name the split-K variant where this M leaves it nothing to split
   // (or no workspace is registered on this device): the default kernel instead -- never when the variant was forced
-  if (rc == VT_ERR_UNSUPPORTED && variant == 33 && g_gemm_variant < 0) return launch(g, GEMM_DEFAULT_VARIANT);
+  if (rc == VT_ERR_UNSUPPORTED && variant == GEMM_SPLITK_VARIANT && g_gemm_variant < 0) return launch(g, GEMM_DEFAULT_VARIANT);
   return rc;
 }
 
@@ -968,16 +927,13 @@ int vt_gemm_ln_dispatch(const void* A, long lda, const void* W, long ldw, const 
        (uintptr_t)Cs | (uintptr_t)stats_out) & 15)
     return VT_ERR_BAD_ALIGN;
   GemmArgs g;
-  g.A = (const bf16_t*)A; g.W = (const bf16_t*)W; g.bias = bias; g.R = nullptr; g.C = C; g.C2 = nullptr;
-  g.lda = lda; g.ldw = ldw; g.ldr = 0; g.ldc = ldc; g.ldc2 = 0;
-  g.M = M; g.N = N; g.K = K; g.grp_rows = 0; g.grp_stride = 0; g.tiles_m = 0; g.tiles_n = 0;
-  g.trace = nullptr;
-  g.drop.thresh = 0; g.drop.seed = 0; g.drop.scale = 1.0f;
+  g.A = (const bf16_t*)A; g.W = (const bf16_t*)W; g.bias = bias; g.C = C;
+  g.lda = lda; g.ldw = ldw; g.ldc = ldc;
+  g.M = M; g.N = N; g.K = K;
   g.ln_mode = ln_mode; g.ln_np = np; g.ln_rows = (int)stat_rows; g.ln_inv_n = 1.0f / (float)row_len; g.ln_eps = eps;
   g.ln_stats = stats_in; g.colv = colv; g.Rs = (const uint16_t*)Rs; g.Cs = (uint16_t*)Cs; g.stats_out = stats_out; g.ldrs = ldrs; g.ldcs = ldcs;
-  g.ksplit = 0; g.reverse = 0; g.c_plane = 0; g.r_f16 = 0; g.c_f16 = 0;
   int variant = g_gemm_variant >= 0 ? g_gemm_variant : vt_gemm_pick_variant(M, N, K, VT_TUNE_KIND(act, 0, 0, 0, ln_mode));
-  if (variant != 15 && variant != 16 && (variant < 18 || variant > 23) && (variant < 28 || variant > 32)) variant = 16;   // only the 256x256-tile kernels
+  if (!(gv::flags(variant) & gv::LN_EPILOGUE)) variant = GEMM_PERSISTENT_VARIANT;   // only the 256x256-tile kernels
   return vt_gemm_ln_launch(g, act, variant, stream);
 }
 
@@ -1008,14 +964,10 @@ int vt_gemm_splitk_dispatch(const void* A, long lda, const void* W, long ldw, vo
   if (M <= 0 || N <= 0 || K <= 0 || (K % 64) || (N % 4) || ksplit < 2 || ksplit > 64 || ksplit > K / 64) return VT_ERR_BAD_SHAPE;
   if ((lda % 8) || (ldw % 8) || (ldc % 4) || (((uintptr_t)A | (uintptr_t)W | (uintptr_t)C | (uintptr_t)ws) & 15)) return VT_ERR_BAD_ALIGN;
   GemmArgs g;
-  g.A = (const bf16_t*)A; g.W = (const bf16_t*)W; g.bias = nullptr; g.R = nullptr; g.C = ws; g.C2 = nullptr;
-  g.lda = lda; g.ldw = ldw; g.ldr = 0; g.ldc = N; g.ldc2 = 0;
-  g.M = M; g.N = N; g.K = K; g.grp_rows = 0; g.grp_stride = 0; g.tiles_m = 0; g.tiles_n = 0;
-  g.trace = nullptr;
-  g.drop.thresh = 0; g.drop.seed = 0; g.drop.scale = 1.0f;
-  g.ln_mode = 0; g.ln_np = 0; g.ln_rows = 0; g.ln_inv_n = 0.f; g.ln_eps = 0.f; g.ln_stats = nullptr; g.colv = nullptr;
-  g.Rs = nullptr; g.Cs = nullptr; g.stats_out = nullptr; g.ldrs = 0; g.ldcs = 0;
-  g.ksplit = ksplit; g.reverse = 0; g.c_plane = (long)M * N; g.r_f16 = 0; g.c_f16 = 0;
+  g.A = (const bf16_t*)A; g.W = (const bf16_t*)W; g.C = ws;
+  g.lda = lda; g.ldw = ldw; g.ldc = N;
+  g.M = M; g.N = N; g.K = K;
+  g.ksplit = ksplit; g.c_plane = (long)M * N;
   const int rc = vt_gemm_v7_launch(g, ACT_NONE, 1, stream, 8);
   if (rc) return rc;
   const long n4 = ((long)M * N + 3) / 4;

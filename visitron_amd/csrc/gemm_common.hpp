@@ -1,20 +1,21 @@
 // Shared by the NT GEMM kernels (gemm_bf16.hip, gemm_v7.hip): argument block and the register epilogue.
 #pragma once
+#include <type_traits>
 #include "common.hpp"
 
 struct GemmArgs {
-  const bf16_t* A;
-  const bf16_t* W;
-  const float* bias;
-  const bf16_t* R;   // residual added after the activation; for ACT_MUL: the factor (saved gelu')
-  void* C;
-  bf16_t* C2;        // optional second output for backward: gelu'(acc + bias) if ACT_GELU, else acc + bias
-  long lda, ldw, ldr, ldc, ldc2;
-  int M, N, K;
-  int grp_rows, grp_stride;  // output row = (m / grp_rows) * grp_stride + m % grp_rows  (0: identity)
-  int tiles_m, tiles_n;
-  unsigned long long* trace; // debug: per-workgroup phase timestamps of the persistent kernel (vt_debug_set_gemm_trace)
-  DropCfg drop;              // dropout on act(acc + bias) BEFORE the residual add (BertSelfOutput / BertOutput /
+  const bf16_t* A = nullptr;
+  const bf16_t* W = nullptr;
+  const float* bias = nullptr;
+  const bf16_t* R = nullptr;   // residual added after the activation; for ACT_MUL: the factor (saved gelu')
+  void* C = nullptr;
+  bf16_t* C2 = nullptr;        // optional second output for backward: gelu'(acc + bias) if ACT_GELU, else acc + bias
+  long lda = 0, ldw = 0, ldr = 0, ldc = 0, ldc2 = 0;
+  int M = 0, N = 0, K = 0;
+  int grp_rows = 0, grp_stride = 0;  // output row = (m / grp_rows) * grp_stride + m % grp_rows  (0: identity)
+  int tiles_m = 0, tiles_n = 0;
+  unsigned long long* trace = nullptr;  // debug: per-workgroup phase timestamps of the persistent kernel (vt_debug_set_gemm_trace)
+  DropCfg drop = {0, 0, 1.0f};  // dropout on act(acc + bias) BEFORE the residual add (BertSelfOutput / BertOutput /
                              // image embedding); element index = m * N + n
   // ---- deferred LayerNorm (the inference path's fused residual + LayerNorm, gemm_v7_ln.hip) ---------------------
   // The residual stream between two sub-layers is the PRE-LayerNorm sum v, kept as fp16 [M, H] (the stream itself: 11
@@ -27,29 +28,29 @@ struct GemmArgs {
   //   ln_mode 2 (producer: out-proj, FFN-down)  v' = A W^T + cb + LN(v)                    LN(v) = (Rs - mean_r) rstd_r gamma
   //                                        (colv) + beta, cb = b + beta (bias); writes v' as fp16 (Cs), bf16 (C) and its
   //                                        partial statistics (stats_out, slices of this tile's columns).
-  int ln_mode;
-  int ln_np;                 // partials per row of ln_stats (H / 128, <= 8)
-  int ln_rows;               // rows per slice of ln_stats / stats_out (>= M, even: slices stay 16-byte aligned)
-  float ln_inv_n, ln_eps;    // 1 / H, LayerNorm epsilon
-  const float* ln_stats;     // [ln_np][ln_rows][2]
-  const float* colv;         // per-column vector, see above
-  const uint16_t* Rs;        // mode 2: the fp16 stream in (row stride ldrs)
-  uint16_t* Cs;              // mode 2: the fp16 stream out (row stride ldcs)
-  float* stats_out;          // mode 2: [N / 128][ln_rows][2]
-  long ldrs, ldcs;
+  int ln_mode = 0;
+  int ln_np = 0;             // partials per row of ln_stats (H / 128, <= 8)
+  int ln_rows = 0;           // rows per slice of ln_stats / stats_out (>= M, even: slices stay 16-byte aligned)
+  float ln_inv_n = 0.f, ln_eps = 0.f;  // 1 / H, LayerNorm epsilon
+  const float* ln_stats = nullptr;  // [ln_np][ln_rows][2]
+  const float* colv = nullptr;      // per-column vector, see above
+  const uint16_t* Rs = nullptr;     // mode 2: the fp16 stream in (row stride ldrs)
+  uint16_t* Cs = nullptr;           // mode 2: the fp16 stream out (row stride ldcs)
+  float* stats_out = nullptr;       // mode 2: [N / 128][ln_rows][2]
+  long ldrs = 0, ldcs = 0;
   // ---- split-K (one-tile-per-workgroup kernel, fp32 partial planes): workgroup (tile, s) reduces K-steps
   // [s * kq, min((s + 1) * kq, K / 64)), kq = ceil(K / 64 / ksplit), and writes plane s of C (c_plane elements apart);
   // a reduce pass sums the planes.  For the shapes whose tile count leaves most of the chip idle and whose K is long:
   // the MLM decoder's dgrad, [4 272, 30 528] x [30 528, 768] = 51 tiles of 256 x 256 with 477 K-steps each.
-  int ksplit;                // 0 / 1: off
-  int reverse;               // persistent kernel: walk the tile order backwards (experiment: consume a > 256 MB operand in the reverse
+  int ksplit = 0;            // 0 / 1: off
+  int reverse = 0;           // persistent kernel: walk the tile order backwards (experiment: consume a > 256 MB operand in the reverse
                              // of the order its producer wrote it, so that the rows still in the Infinity Cache are read first)
-  long c_plane;
+  long c_plane = 0;
   // ---- fp16 copies of the residual stream in the seven-launch (training) layer ------------------------------------
   // r_f16: the residual operand R holds fp16 (the previous LayerNorm's output, kept beside its bf16 copy);
   // c_f16: C is written as fp16 (saturating): the pre-LayerNorm sum dense(h) + bias + residual.  Same bytes as bf16, three
   // more significant bits where the stream is rounded twice per sub-layer.
-  int r_f16, c_f16;
+  int r_f16 = 0, c_f16 = 0;
   // ---- the residual as a LayerNorm that was never written out (training layer, vt_layer_acts::ln_residual_mode) ------
   // r_mean != null: R holds the fp16 PRE-LayerNorm sum v of the previous sub-layer (r_f16 is set) and the value added is
   // LayerNorm(v) = (v - r_mean[row]) * r_rstd[row] * r_gamma[col] + r_beta[col], the statistics being the ones the
@@ -70,6 +71,9 @@ struct GemmArgs {
   unsigned* sk_err = nullptr;   // bounded waits that ran out (host: vt_gemm_shared_tile_timeouts)
   int sk_parts = 0;
 };
+// passed to the kernels by value; a new member takes a default initialiser above and moves the size on purpose
+static_assert(std::is_trivially_copyable<GemmArgs>::value, "GemmArgs is a kernel argument");
+static_assert(sizeof(GemmArgs) == 304, "GemmArgs layout");
 #define V8_SK_WGS_PER_XCD 32                   // workgroups per XCD the region is laid out for (a 256-CU grid)
 #define V8_SK_PART_BYTES (256 * 64 * 16)       // one part's accumulators: 256 lanes x 64 registers of 16 B
 #define V8_SK_REGION_BYTES ((long)8 * V8_SK_WGS_PER_XCD * V8_SK_PART_BYTES + 4096)   // + the counters and the error word
@@ -82,6 +86,27 @@ enum { ACT_NONE = 0, ACT_GELU = 1, ACT_TANH = 2, ACT_MUL = 3 };  // MUL: out = a
 #define GEMM_TILE_BYTES (128 * 64 * 2)
 #define GEMM_LDS_BYTES (4 * GEMM_TILE_BYTES)
 #define GEMM_DEFAULT_VARIANT 1
+#define GEMM_PERSISTENT_VARIANT 16   // persistent 256-row tiles: the deferred-LayerNorm fallback, the tail split
+#define GEMM_SPLITK_VARIANT 33
+
+// ---- what a variant number names: gemm_variants.def, one line per variant (gv::find(id)->family, gv::flags(id) & gv::FLAG) -------
+namespace gv {
+enum Family { V2_RING2, V2_RING3, V6, V4_192, V4_256, V5, V7, V8, V8_SHARED, SPLITK_EPI, V10, V11, V12 };
+enum : unsigned { PERSISTENT = 1, NEEDS_WORKSPACE = 2, LN_EPILOGUE = 4, BF16_IO_ONLY = 8, TUNE_CANDIDATE = 16, TUNE_CANDIDATE_STREAMK_ONLY = 32 };
+constexpr unsigned PLAIN_TWIN(unsigned id) { return id << 8; }
+struct Variant { int id; Family family; int mtn; unsigned flags; };
+constexpr Variant TABLE[] = {
+#define VT_GEMM_VARIANT(id, family, mtn, flags) {id, family, mtn, flags},
+#include "gemm_variants.def"
+#undef VT_GEMM_VARIANT
+};
+static inline const Variant* find(int id) {   // null: no such variant in this build
+  for (const Variant& v : TABLE)
+    if (v.id == id) return &v;
+  return nullptr;
+}
+static inline unsigned flags(int id) { const Variant* v = find(id); return v ? v->flags : 0; }
+}  // namespace gv
 
 // ---- launchers that cross a translation unit (called from vt_gemm_dispatch / vt_gemm_ln_dispatch, gemm_bf16.hip) ----------
 // gemm_v7.hip: 256x256-tile kernels, tile height 32 * mtn; v8 is the persistent form (sk: with the stream-K region)
@@ -89,6 +114,8 @@ int vt_gemm_v7_launch(const GemmArgs& g, int act, int out_f32, hipStream_t strea
 int vt_gemm_v8_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stream, int mtn, bool sk = false);
 int vt_gemm_splitk_tiles_launch(const GemmArgs& g, int act, int out_f32, int ks, hipStream_t stream);
 int vt_gemm_persistent_cus();               // the device's CU count less the reserved ones (vt_gemm_reserve_cus)
+// workgroups of a persistent launch (<= 0: no device); settles the stream-K region.  (Internal: not an exported symbol.)
+__attribute__((visibility("hidden"))) int vt_gemm_v8_grid(int tiles, int& sk_parts);
 int vt_gemm_v8_take_region(GemmArgs& g);    // shared-tile workspace of this launch (0: none registered)
 // gemm_v7_ln.hip: the deferred-LayerNorm epilogues (GemmArgs::ln_mode)
 int vt_gemm_ln_launch(const GemmArgs& g, int act, int variant, hipStream_t stream);
@@ -97,6 +124,32 @@ int vt_gemm_v10_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stre
 int vt_gemm_v11_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stream);           // gemm_v11.hip (eight waves on shared 256x256 stages)
 int vt_gemm_v12_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stream, int mtn);  // gemm_v12.hip (short tiles on three operand stages)
 #endif
+
+// operand panels are addressed with 32-bit byte offsets inside a tile's row panel (the 256x256-tile kernels)
+static inline bool v7_operands_fit(const GemmArgs& g) {
+  return !(g.K & 63) && 256L * g.lda * 2 + 2L * g.K < (1L << 31) && 256L * g.ldw * 2 + 2L * g.K < (1L << 31);
+}
+
+// (act, out_f32) -> compile-time constants: calls f(std::integral_constant<int, ACT>, std::integral_constant<bool, OUT_F32>).
+// MUL_F32 = false: ACT_MUL with fp32 output is refused and f is not instantiated for it.
+template <bool MUL_F32 = true, typename F>
+static inline int with_act_out(int act, int out_f32, F&& f) {
+  using N = std::false_type;
+  using T = std::true_type;
+  switch (act * 2 + (out_f32 ? 1 : 0)) {
+    case 0: return f(std::integral_constant<int, ACT_NONE>{}, N{});
+    case 1: return f(std::integral_constant<int, ACT_NONE>{}, T{});
+    case 2: return f(std::integral_constant<int, ACT_GELU>{}, N{});
+    case 3: return f(std::integral_constant<int, ACT_GELU>{}, T{});
+    case 4: return f(std::integral_constant<int, ACT_TANH>{}, N{});
+    case 5: return f(std::integral_constant<int, ACT_TANH>{}, T{});
+    case 6: return f(std::integral_constant<int, ACT_MUL>{}, N{});
+    case 7:
+      if constexpr (MUL_F32) return f(std::integral_constant<int, ACT_MUL>{}, T{});
+      return VT_ERR_UNSUPPORTED;
+    default: return VT_ERR_UNSUPPORTED;
+  }
+}
 
 template <int ACT>
 __device__ __forceinline__ float apply_act(float x) {

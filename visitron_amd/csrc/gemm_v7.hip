@@ -1,4 +1,4 @@
-// NT GEMM, 256x256 tile with 128x128 wave tiles and AGPR accumulators (variants 15, 16, 18 .. 23 of vt_gemm_dispatch):
+// NT GEMM, 256x256 tile with 128x128 wave tiles and AGPR accumulators (families V7, V8, V8_SHARED and SPLITK_EPI of gemm_variants.def):
 // launchers of the kernels in gemm_v7_kernels.hpp with the plain epilogues.
 #include <atomic>
 #include <cstdlib>
@@ -19,8 +19,8 @@ int vt_gemm_persistent_cus() {
 // ---- workspace of the stream-K region (GemmArgs::sk_parts) ------------------------------------------------------------
 // Caller-owned device memory, registered per device (vt_gemm_set_workspace): `regions` regions of V8_SK_REGION_BYTES, each
 // = 8 x 32 workgroup slots x 256 KiB of fp32 accumulators, then 256 arrival counters and one error counter (the
-// caller hands the memory over ZEROED; the kernels leave the counters at zero).  Launches take the regions round-robin, so
-// that many launches may be in flight on different streams of one device; launches of one stream never overlap.
+// caller hands the memory over ZEROED; the kernels leave the counters at zero).  Regions alternate per launch (one counter for
+// all devices and streams); only launches of ONE stream are ordered against the reuse of a region.
 struct SkWorkspace { char* base; int regions; };
 static SkWorkspace g_sk_ws[VT_MAX_DEVICES];
 static std::atomic<unsigned> g_sk_ctr{0};
@@ -83,29 +83,32 @@ void* vt_gemm_take_scratch(long bytes) {
   return g_sk_ws[dev].base + (long)(g_sk_ctr.fetch_add(1) % (unsigned)g_sk_ws[dev].regions) * V8_SK_REGION_BYTES;
 }
 
-static int v8_grid(int tiles) {
+// Workgroups of a persistent launch: one per CU at most.  The stream-K region (sk_parts > 1) spreads a chunk's tiles over every
+// workgroup of the XCD: the whole grid even for fewer tiles than CUs -- unless the device has more CUs than the region has
+// slots (laid out for 32 workgroups per XCD), which switches the region off.
+int vt_gemm_v8_grid(int tiles, int& sk_parts) {
   const int cus = vt_gemm_persistent_cus();
-  if (cus <= 0) return -1;
-  return tiles < cus ? tiles : cus;
+  if (sk_parts > 1 && cus > 8 * V8_SK_WGS_PER_XCD) sk_parts = 0;
+  return cus <= 0 ? -1 : (sk_parts > 1 || tiles > cus) ? cus : tiles;
 }
 
 template <int ACT, bool OUT_F32>
 static int launch_v8(const GemmArgs& g, hipStream_t stream, int mtn, bool shared_tiles) {
   GemmArgs g8 = g;
   g8.tiles_n = (g.N + 255) / 256;
-  if ((g.K & 63) || 256L * g.lda * 2 + 2L * g.K >= (1L << 31) || 256L * g.ldw * 2 + 2L * g.K >= (1L << 31)) return VT_ERR_UNSUPPORTED;
+  if (!v7_operands_fit(g)) return VT_ERR_UNSUPPORTED;
   // bf16 output in whole 64-column slabs without row remap: the straight-line epilogue, specialised on the residual.
   // (Round 5 kept residual GEMMs with N % 128 != 0 away from it: a wave whose second column half lies past N never waited
   // for that half's ring loads.  Round 6 drains the ring in the kernel -- V7_HALF's else branch -- and the guard is gone;
   // tests/test_gpu_round5.py runs N = 832 / 384 / 640 with a residual and with ACT_MUL on every 256x256-tile variant.)
   const bool fast = !OUT_F32 && (g.N & 63) == 0 && g.grp_rows == 0;
   if (ACT == ACT_MUL && !g.R) return VT_ERR_NULL;
-  // variants 28 .. 32 need vt_gemm_set_workspace; the register-epilogue kernels do not share tiles (they run as 16 .. 21)
+  // the shared-tile variants need vt_gemm_set_workspace; the register-epilogue kernels do not share tiles (they run as their plain twins)
   if (shared_tiles && !vt_gemm_has_workspace()) return VT_ERR_UNSUPPORTED;
   if (!fast || OUT_F32 || ACT == ACT_TANH) mtn = 8;   // the shorter tiles exist for the encoder's own (bf16, fast-epilogue) shapes
   else if (g.r_mean && mtn == 8) mtn = 7;             // a rebuilt LayerNorm residual: not in the 256-row instantiation (v7_epilogue_fast)
   // the stream-K region exists in the fast-epilogue kernels on 160- and 128-row tiles (gemm_nt_bf16_v8: SK_OK); the other
-  // variants of 28 .. 32 run as their plain twins
+  // shared-tile variants run as their plain twins
   if (shared_tiles && fast && mtn <= 5 && !v8_take_region(g8)) return VT_ERR_UNSUPPORTED;
   const int th = 32 * mtn;
   g8.tiles_m = (g.M + th - 1) / th;
@@ -113,15 +116,8 @@ static int launch_v8(const GemmArgs& g, hipStream_t stream, int mtn, bool shared
     static const int rev_k = [] { const char* e = getenv("VT_GEMM_REVERSE_K"); return e ? atoi(e) : 0; }();
     g8.reverse = (rev_k > 0 && g.K >= rev_k) ? 1 : 0;
   }
-  int grid = v8_grid(g8.tiles_m * g8.tiles_n);
+  const int grid = vt_gemm_v8_grid(g8.tiles_m * g8.tiles_n, g8.sk_parts);
   if (grid <= 0) return VT_ERR_HIP;
-  // the stream-K region spreads a chunk's tiles over every workgroup of the XCD: launch the whole grid even for fewer
-  // tiles than CUs (the region's slots are laid out for 32 workgroups per XCD)
-  if (g8.sk_parts > 1) {
-    const int cus = vt_gemm_persistent_cus();
-    if (cus > 8 * V8_SK_WGS_PER_XCD) g8.sk_parts = 0;
-    else grid = cus;
-  }
   const bool has_r = g.R || ACT == ACT_MUL;
   void (*kern)(GemmArgs) = nullptr;
   if (!fast) kern = gemm_nt_bf16_v8<ACT, OUT_F32, false, false>;
@@ -141,8 +137,7 @@ template <int ACT, bool OUT_F32>
 static int launch_v7(const GemmArgs& g, hipStream_t stream, int mtn) {
   GemmArgs g7 = g;
   g7.tiles_n = (g.N + 255) / 256;
-  // operand panels are addressed with 32-bit byte offsets inside a tile's row panel
-  if ((g.K & 63) || 256L * g.lda * 2 + 2L * g.K >= (1L << 31) || 256L * g.ldw * 2 + 2L * g.K >= (1L << 31)) return VT_ERR_UNSUPPORTED;
+  if (!v7_operands_fit(g)) return VT_ERR_UNSUPPORTED;
   const bool fast = !OUT_F32 && (g.N & 63) == 0 && g.grp_rows == 0;   // as in launch_v8
   if (ACT == ACT_MUL && !g.R) return VT_ERR_NULL;
   if (!fast || OUT_F32 || ACT == ACT_TANH) mtn = 8;
@@ -213,7 +208,7 @@ static int launch_splitk_tiles(const GemmArgs& g, int ks, hipStream_t stream) {
   gs.tiles_m = (g.M + 255) / 256;
   gs.tiles_n = (g.N + 255) / 256;
   const int ntile = gs.tiles_m * gs.tiles_n;
-  if ((g.K & 63) || 256L * g.lda * 2 + 2L * g.K >= (1L << 31) || 256L * g.ldw * 2 + 2L * g.K >= (1L << 31)) return VT_ERR_UNSUPPORTED;
+  if (!v7_operands_fit(g)) return VT_ERR_UNSUPPORTED;
   float* ws = (float*)vt_gemm_take_scratch((long)ks * ntile * V8_SK_PART_BYTES);
   if (!ws) return VT_ERR_UNSUPPORTED;
   gs.sk_ws = ws;
@@ -228,34 +223,14 @@ static int launch_splitk_tiles(const GemmArgs& g, int ks, hipStream_t stream) {
 }
 
 int vt_gemm_splitk_tiles_launch(const GemmArgs& g, int act, int out_f32, int ks, hipStream_t stream) {
-  switch (act * 2 + (out_f32 ? 1 : 0)) {
-    case 0: return launch_splitk_tiles<ACT_NONE, false>(g, ks, stream);
-    case 1: return launch_splitk_tiles<ACT_NONE, true>(g, ks, stream);
-    case 2: return launch_splitk_tiles<ACT_GELU, false>(g, ks, stream);
-    case 3: return launch_splitk_tiles<ACT_GELU, true>(g, ks, stream);
-    case 4: return launch_splitk_tiles<ACT_TANH, false>(g, ks, stream);
-    case 5: return launch_splitk_tiles<ACT_TANH, true>(g, ks, stream);
-    case 6: return launch_splitk_tiles<ACT_MUL, false>(g, ks, stream);
-    case 7: return launch_splitk_tiles<ACT_MUL, true>(g, ks, stream);
-    default: return VT_ERR_UNSUPPORTED;
-  }
+  return with_act_out(act, out_f32, [&](auto A, auto O) { return launch_splitk_tiles<decltype(A)::value, decltype(O)::value>(g, ks, stream); });
 }
 
 int vt_gemm_v8_launch(const GemmArgs& g, int act, int out_f32, hipStream_t stream, int mtn, bool sk) {
 #ifdef V7_ONE
   return launch_v8<ACT_NONE, false>(g, stream, mtn, sk);
 #else
-  switch (act * 2 + (out_f32 ? 1 : 0)) {
-    case 0: return launch_v8<ACT_NONE, false>(g, stream, mtn, sk);
-    case 1: return launch_v8<ACT_NONE, true>(g, stream, mtn, sk);
-    case 2: return launch_v8<ACT_GELU, false>(g, stream, mtn, sk);
-    case 3: return launch_v8<ACT_GELU, true>(g, stream, mtn, sk);
-    case 4: return launch_v8<ACT_TANH, false>(g, stream, mtn, sk);
-    case 5: return launch_v8<ACT_TANH, true>(g, stream, mtn, sk);
-    case 6: return launch_v8<ACT_MUL, false>(g, stream, mtn, sk);
-    case 7: return launch_v8<ACT_MUL, true>(g, stream, mtn, sk);
-    default: return VT_ERR_UNSUPPORTED;
-  }
+  return with_act_out(act, out_f32, [&](auto A, auto O) { return launch_v8<decltype(A)::value, decltype(O)::value>(g, stream, mtn, sk); });
 #endif
 }
 
@@ -263,16 +238,6 @@ int vt_gemm_v7_launch(const GemmArgs& g, int act, int out_f32, hipStream_t strea
 #ifdef V7_ONE
   return launch_v7<ACT_NONE, false>(g, stream, mtn);
 #else
-  switch (act * 2 + (out_f32 ? 1 : 0)) {
-    case 0: return launch_v7<ACT_NONE, false>(g, stream, mtn);
-    case 1: return launch_v7<ACT_NONE, true>(g, stream, mtn);
-    case 2: return launch_v7<ACT_GELU, false>(g, stream, mtn);
-    case 3: return launch_v7<ACT_GELU, true>(g, stream, mtn);
-    case 4: return launch_v7<ACT_TANH, false>(g, stream, mtn);
-    case 5: return launch_v7<ACT_TANH, true>(g, stream, mtn);
-    case 6: return launch_v7<ACT_MUL, false>(g, stream, mtn);
-    case 7: return launch_v7<ACT_MUL, true>(g, stream, mtn);
-    default: return VT_ERR_UNSUPPORTED;
-  }
+  return with_act_out(act, out_f32, [&](auto A, auto O) { return launch_v7<decltype(A)::value, decltype(O)::value>(g, stream, mtn); });
 #endif
 }

@@ -14,13 +14,8 @@ static int launch_ln(const GemmArgs& g, int persistent, int mtn, hipStream_t str
   void (*kern)(GemmArgs) = nullptr;
   int grid = tiles;
   if (persistent) {
-    const int cus = vt_gemm_persistent_cus();
-    if (cus <= 0) return VT_ERR_HIP;
-    grid = tiles < cus ? tiles : cus;
-    if (ga.sk_parts > 1) {   // the stream-K region: the whole grid (launch_v8 in gemm_v7.hip)
-      if (cus > 8 * V8_SK_WGS_PER_XCD) ga.sk_parts = 0;
-      else grid = cus;
-    }
+    grid = vt_gemm_v8_grid(tiles, ga.sk_parts);
+    if (grid <= 0) return VT_ERR_HIP;
     switch (mtn) {
       case 8: kern = gemm_nt_bf16_v8<ACT, false, true, false, 8, LNM>; break;
       case 7: kern = gemm_nt_bf16_v8<ACT, false, true, false, 7, LNM>; break;
@@ -42,25 +37,13 @@ static int launch_ln(const GemmArgs& g, int persistent, int mtn, hipStream_t str
   return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
 }
 
-// variant: the numbering of vt_gemm_dispatch (15 / 22 / 23: one tile per workgroup on 256- / 224- / 192-row tiles; 16, 18 .. 21:
-// persistent on 256- .. 128-row tiles)
+// variant: a number of gemm_variants.def with LN_EPILOGUE (vt_gemm_ln_dispatch sends the others to the persistent 256-row kernel)
 int vt_gemm_ln_launch(const GemmArgs& g, int act, int variant, hipStream_t stream) {
-  int persistent, mtn;
-  const bool sk = variant >= 28 && variant <= 32;   // the persistent kernel sharing its left-over tiles (gemm_v7.hip)
-  if (sk) variant = variant == 28 ? 16 : variant - 11;   // 29 .. 32 -> 18 .. 21
-  switch (variant) {
-    case 15: persistent = 0; mtn = 8; break;
-    case 22: persistent = 0; mtn = 7; break;
-    case 23: persistent = 0; mtn = 6; break;
-    case 16: persistent = 1; mtn = 8; break;
-    case 18: persistent = 1; mtn = 7; break;
-    case 19: persistent = 1; mtn = 6; break;
-    case 20: persistent = 1; mtn = 5; break;
-    case 21: persistent = 1; mtn = 4; break;
-    default: return VT_ERR_UNSUPPORTED;
-  }
-  if ((g.K & 63) || g.K < 128 || (g.N & 127) || 256L * g.lda * 2 + 2L * g.K >= (1L << 31) || 256L * g.ldw * 2 + 2L * g.K >= (1L << 31))
-    return VT_ERR_UNSUPPORTED;
+  const gv::Variant* v = gv::find(variant);
+  if (!v || !(v->flags & gv::LN_EPILOGUE)) return VT_ERR_UNSUPPORTED;
+  const int persistent = (v->flags & gv::PERSISTENT) ? 1 : 0, mtn = v->mtn;
+  const bool sk = v->family == gv::V8_SHARED;   // the persistent kernel sharing its left-over tiles (gemm_v7.hip)
+  if (g.K < 128 || (g.N & 127) || !v7_operands_fit(g)) return VT_ERR_UNSUPPORTED;
   if (g.ln_mode == 1) {
     if (act == ACT_NONE) return launch_ln<ACT_NONE, 1>(g, persistent, mtn, stream, sk);
     if (act == ACT_GELU) return launch_ln<ACT_GELU, 1>(g, persistent, mtn, stream, sk);

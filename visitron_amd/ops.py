@@ -5,6 +5,7 @@ hot path runs in ``libvisitron_hip.so``.  Every function raises on CPU tensors.
 """
 import ctypes
 import os
+import re
 
 import torch
 
@@ -234,16 +235,33 @@ def encoder_forward_ln(layer_weights, stream_a, stream_b, qkv, ctx, mid, mask, m
     _lib.check(rc, "vt_encoder_forward_ln_bf16")
 
 
-# 128x128 (4 / 8 waves), 256x192, 256x256, 256x256 phased (BK32, 4-stage ring), 256x256 with 128x128 wave tiles
-# and AGPR accumulators (15: one tile per workgroup, 16: persistent; 18 .. 21: the persistent kernel on 224- / 192- / 160- / 128-row tiles; 22 / 23: the one-tile-per-workgroup kernel on 224- / 192-row tiles,
-# which balance the rounds over the 256 CUs when the 256-row tiling leaves the last round mostly empty).
-# 31 / 32: the persistent kernel on 160- / 128-row tiles with a STREAM-K region (round 6; 28 .. 30 exist as numbers and run as
-# their plain twins 16 / 18 / 19).  Measured negative on MI355X at every row count tried (profiles/r06/streamk_ab.txt: +10 .. +47 %
-# against the best plain variant, parity at best): opt-in candidates (VT_GEMM_STREAMK=1), never timed by default.
+# ---- the GEMM kernel variants: csrc/gemm_variants.def is the list (one line per variant, described there) ---------------------
+_VARIANT_FLAGS = ("PERSISTENT", "NEEDS_WORKSPACE", "LN_EPILOGUE", "BF16_IO_ONLY", "TUNE_CANDIDATE", "TUNE_CANDIDATE_STREAMK_ONLY")
+_VARIANT_LINE = re.compile(r"VT_GEMM_VARIANT\((\d+), (\w+), (\d), (\w+(?: \| \w+)*)(?: \| PLAIN_TWIN\((\d+)\))?\)\s*(?://.*)?")
+
+
+def _parse_variants(text):
+    """gemm_variants.def -> {id: {"family", "mtn", "flags" (frozenset), "twin" (id or None)}} in file order, the variants of the
+    experimental build (24 .. 27) included.  The line format is closed: anything else raises."""
+    out = {}
+    for n, line in enumerate(text.splitlines(), 1):
+        line = line.strip()
+        if not line or line.startswith("//") or line in ("#ifdef VT_EXPERIMENTAL_GEMM", "#endif"):
+            continue
+        m = _VARIANT_LINE.fullmatch(line)
+        flags = () if not m or m.group(4) == "0" else m.group(4).split(" | ")
+        if not m or int(m.group(1)) in out or set(flags) - set(_VARIANT_FLAGS):
+            raise ImportError("visitron_amd: line %d of csrc/gemm_variants.def is malformed or names an unknown flag: `%s`" % (n, line))
+        out[int(m.group(1))] = {"family": m.group(2), "mtn": int(m.group(3)), "flags": frozenset(flags),
+                                "twin": m.group(5) and int(m.group(5))}
+    return out
+
+
+GEMM_VARIANTS = _parse_variants(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "gemm_variants.def")).read())
+_variants_with = lambda flag: tuple(v for v, e in GEMM_VARIANTS.items() if flag in e["flags"])
+# the stream-K variants measured negative on MI355X at every row count tried: opt-in candidates, never timed by default
 STREAMK = os.environ.get("VT_GEMM_STREAMK", "0") == "1"
-# 33: split-K of the one-tile kernel with the whole epilogue behind the ordered plane sum (small M, long K; needs the workspace)
-# 35: the 128x128-tile kernel on a three-stage ring (long K, fewer tiles than CUs)
-GEMM_CANDIDATES = (1, 14, 9, 10, 11, 15, 16, 18, 19, 20, 21, 22, 23, 33, 35) + ((31, 32) if STREAMK else ())   # (24 .. 27: the measured-negative redesigns of round 4 live in tools/experiments, outside the product library)
+GEMM_CANDIDATES = _variants_with("TUNE_CANDIDATE") + (_variants_with("TUNE_CANDIDATE_STREAMK_ONLY") if STREAMK else ())   # file order is timing order
 
 
 # -1: shape table / heuristic; -2: the same plus the tail launch of the persistent kernel's last round (VT_GEMM_TAIL_SPLIT=1)
@@ -255,13 +273,13 @@ def set_gemm_variant(v):
     if int(v) in SHARED_TILE_VARIANTS:
         ensure_gemm_workspace()
     _lib.load().vt_debug_set_gemm_variant(int(AUTO_VARIANT if v == -1 else v))
-# The persistent kernel (16) launches one workgroup per CU and needs every CU to itself (512 registers per wave, 132 KiB
+# The persistent kernel launches one workgroup per CU and needs every CU to itself (512 registers per wave, 132 KiB
 # of LDS): a collective running beside it on a few CUs makes the workgroups mapped to those CUs wait for a whole kernel
 # time.  Data-parallel training (gradient all-reduce overlapped with the backward) therefore tunes without it; the
-# one-tile-per-workgroup forms of the same kernel (15, 22, 23) are within 1 % over the step and simply queue their tiles.
+# one-tile-per-workgroup forms of the same kernel are within 1 % over the step and simply queue their tiles.
 PERSISTENT_GEMM_OK = True
-PERSISTENT_VARIANTS = (16, 18, 19, 20, 21, 28, 29, 30, 31, 32)
-SHARED_TILE_VARIANTS = (28, 29, 30, 31, 32, 33)   # variants that need the GEMM workspace below (stream-K region; split-K planes)
+PERSISTENT_VARIANTS = _variants_with("PERSISTENT")
+SHARED_TILE_VARIANTS = _variants_with("NEEDS_WORKSPACE")   # the GEMM workspace below (stream-K region; split-K planes)
 
 
 def multi_rank_gemm_policy(environ=None):
@@ -301,7 +319,8 @@ def tune_kind(act, residual=False, pre_act=False, out_f32=False, ln_mode=0):
     return int(act) | (16 if (residual or act == ACT_MUL) else 0) | (32 if pre_act else 0) | (64 if out_f32 else 0) | (int(ln_mode) << 8)
 
 
-LN_GEMM_CANDIDATES = (15, 16, 18, 19, 20, 21, 22, 23) + ((31, 32) if STREAMK else ())   # the deferred-LayerNorm epilogues exist on the 256x256-tile kernels
+# the deferred-LayerNorm epilogues exist on the 256x256-tile kernels
+LN_GEMM_CANDIDATES = tuple(v for v in GEMM_CANDIDATES if "LN_EPILOGUE" in GEMM_VARIANTS[v]["flags"])
 TUNE_ROUNDS = 3          # interleaved timing rounds per candidate; a candidate's time is the MEDIAN of its rounds
 TUNE_KEEP_DEFAULT = 0.03   # the committed default stays unless a candidate beats it by more than this fraction
 _defaults = None
@@ -349,13 +368,13 @@ def autotune_linear(M, N, K, act=ACT_NONE, residual=False, pre_act=False, device
     if key in _tuned:
         return _tuned[key]
     lib = _lib.load()
-    have_ws = ensure_gemm_workspace(device)   # (before any variant is registered: 28 .. 33 need it at launch time)
+    have_ws = ensure_gemm_workspace(device)   # (before any variant is registered: SHARED_TILE_VARIANTS need it at launch time)
     # The training layer's residual GEMMs (out-proj, FFN-down) read an fp16 residual and write the fp16 pre-LayerNorm sum
-    # (F16_STREAM); the grouped epilogue of variants 9 / 10 is bf16-only and the library would silently run variant 1 in their
-    # place -- a kernel never timed for the shape.  Such kinds are tuned with the dtypes they run with, without 9 / 10.
+    # (F16_STREAM); the grouped epilogue of the BF16_IO_ONLY variants cannot and the library would silently run the default
+    # variant in their place -- a kernel never timed for the shape.  Such kinds are tuned with the dtypes they run with, without them.
     f16_io = F16_STREAM and residual and act == ACT_NONE and not out_f32 and not pre_act and not ln_mode
     usable = lambda v: (v is not None and (v not in PERSISTENT_VARIANTS or PERSISTENT_GEMM_OK)
-                        and not (f16_io and v in (9, 10)) and (have_ws or v not in SHARED_TILE_VARIANTS))
+                        and not (f16_io and "BF16_IO_ONLY" in GEMM_VARIANTS[v]["flags"]) and (have_ws or v not in SHARED_TILE_VARIANTS))
     saved = _tune_file_table().get("%d,%d,%d,%d" % key)
     if usable(saved):   # VT_TUNE_FILE: a previous run's choices
         lib.vt_gemm_tune(M, N, K, kind, int(saved))
@@ -1135,8 +1154,8 @@ _gemm_ws = {}
 
 def ensure_gemm_workspace(device=None):
     """Register the shared-tile workspace of the persistent GEMM (vt_gemm_set_workspace) on `device`, once: VT_GEMM_WS_REGIONS
-    regions (default 2; 0: none -- kernel variants 28 .. 32 are then refused and the autotuner leaves them out) of ~96 MiB,
-    zeroed, owned by this module for the life of the process."""
+    regions (default 2; 0: none -- SHARED_TILE_VARIANTS are then refused and the autotuner leaves them out) of 64 MiB + 4 KiB
+    (vt_gemm_workspace_region_bytes), zeroed, owned by this module for the life of the process."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
