@@ -306,6 +306,33 @@ int vt_adamw_flat(float* p, const float* g, float* m, float* v, void* p_bf16, in
  * the bytes of the reference's fp32 DDP buckets, pretrain.py:96-102,191, over xGMI); moments and master weights stay fp32. */
 int vt_adamw_flat_g16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16, int64_t n, float lr, float step_size,
                       float b1, float b2, float eps, float wd, float grad_scale, vt_stream_t stream);
+/* ---- multi-tensor optimizer step, gradient norm and clip (ABI 14) ------------------------------------------------------
+ * The reference's own loops step a torch-side optimizer over a parameter LIST (pretrain.py:128-130,192: pytorch-transformers
+ * AdamW; agent.py:129,511-518: two clip_grad_norm at 40.0, two torch.optim.Adam).  These four entry points serve such a list
+ * in a number of launches that does not depend on it; each is exactly one kernel launch.
+ * table: n_chunks entries of VT_OPTIM_ENTRY_WORDS uint64 in device memory: byte addresses of the chunk's first p, g, m, v
+ * element (fp32, 4-byte aligned is enough; 0 where the entry point does not use it), the chunk's element count
+ * (1 .. VT_OPTIM_CHUNK) and the index of its hyper-parameter slot.  A tensor is cut at multiples of VT_OPTIM_CHUNK elements.
+ * Chunks whose addresses are all multiples of 16 move 16 bytes per lane, the others one element per lane; any count works.
+ * The caller keeps table, hyper and the tensors alive and unchanged until the launch has run. */
+#define VT_OPTIM_CHUNK 65536
+#define VT_OPTIM_ENTRY_WORDS 6
+#define VT_OPTIM_HYPER_FLOATS 8
+/* Per element, gg = g * coef:  m = b1 m + omb1 gg;  v = b2 v + omb2 gg^2;  p -= step_size * m / (sqrt(v) * rsbc2 + eps);
+ * if (lrwd > 0) p -= lrwd * p.  hyper: VT_OPTIM_HYPER_FLOATS floats per slot in device memory, in the order b1, omb1 = 1 - b1,
+ * b2, omb2 = 1 - b2, step_size, rsbc2, eps, lrwd = lr * wd, each formed in double on the host and rounded once.
+ * pytorch-transformers AdamW: rsbc2 = 1, step_size = lr * sqrt(1 - b2^t) / (1 - b1^t) (lr without correct_bias);
+ * torch.optim.Adam: rsbc2 = 1 / sqrt(1 - b2^t), step_size = lr / (1 - b1^t), lrwd = 0.
+ * coef = *grad_coef_dev where that is not NULL (the clip coefficient vt_norm_finish wrote), else grad_coef. */
+int vt_multi_adam(const uint64_t* table, int64_t n_chunks, const float* hyper, float grad_coef, const float* grad_coef_dev,
+                  vt_stream_t stream);
+/* partials[c] (n_chunks doubles) = sum of g^2 over chunk c, every term in fp64; no atomics. */
+int vt_multi_sumsq(const uint64_t* table, int64_t n_chunks, void* partials, vt_stream_t stream);
+/* One workgroup adds the partials in a fixed order in fp64 and writes two floats, torch.nn.utils.clip_grad_norm_'s rule:
+ * out[0] = total_norm = sqrt(sum), out[1] = clip_coef = min(1, max_norm / (total_norm + 1e-6)).  n_chunks may be 0. */
+int vt_norm_finish(const void* partials, int64_t n_chunks, float max_norm, float* out, vt_stream_t stream);
+/* g *= *coef_dev over the table. */
+int vt_multi_scale(const uint64_t* table, int64_t n_chunks, const float* coef_dev, vt_stream_t stream);
 /* out[r, 64 h + d] = x[r, 64 h + d] * head_scale[h] (bf16 rows of nh * 64 columns): the reference's head_mask
  * (oscar/modeling_bert.py:65-66) on a context tensor or, on the way back, on its gradient (training path). */
 int vt_scale_heads_bf16(const void* x, int64_t ldx, void* out, int64_t ldo, int64_t rows, int nh, const float* head_scale,

@@ -22,7 +22,7 @@ const char* vt_error_string(int code) {
   }
 }
 
-int vt_abi_version(void) { return 13; }
+int vt_abi_version(void) { return 14; }
 
 // attention-probability dropout: 16-bit fields (default since ABI 12: p in steps of 1/65536, two keys per hash word -- the
 // reference's nn.Dropout(0.1) runs as 0.100006) or 8-bit fields (rounds 4-5's form: steps of 1/256, four keys per hash word,
@@ -199,6 +199,24 @@ int vt_adamw_flat(float* p, const float* g, float* m, float* v, void* p_bf16, in
 int vt_adamw_flat_g16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16, int64_t n, float lr, float step_size,
                       float b1, float b2, float eps, float wd, float grad_scale, vt_stream_t stream) {
   return vt_adamw_dispatch(p, g_bf16, 1, m, v, p_bf16, n, lr, step_size, b1, b2, eps, wd, grad_scale, (hipStream_t)stream);
+}
+
+// ---- multi-tensor optimizer step, gradient norm and clip (ABI 14) --------------------------------------------------
+int vt_multi_adam(const uint64_t* table, int64_t n_chunks, const float* hyper, float grad_coef, const float* grad_coef_dev,
+                  vt_stream_t stream) {
+  return vt_multi_adam_dispatch(table, n_chunks, hyper, grad_coef, grad_coef_dev, (hipStream_t)stream);
+}
+
+int vt_multi_sumsq(const uint64_t* table, int64_t n_chunks, void* partials, vt_stream_t stream) {
+  return vt_multi_sumsq_dispatch(table, n_chunks, partials, (hipStream_t)stream);
+}
+
+int vt_norm_finish(const void* partials, int64_t n_chunks, float max_norm, float* out, vt_stream_t stream) {
+  return vt_norm_finish_dispatch(partials, n_chunks, max_norm, out, (hipStream_t)stream);
+}
+
+int vt_multi_scale(const uint64_t* table, int64_t n_chunks, const float* coef_dev, vt_stream_t stream) {
+  return vt_multi_scale_dispatch(table, n_chunks, coef_dev, (hipStream_t)stream);
 }
 
 int vt_mask_tokens(const int64_t* input_ids, const uint8_t* special_mask, const int64_t* token_classes, const float* u_mask,

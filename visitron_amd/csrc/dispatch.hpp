@@ -128,6 +128,13 @@ int vt_ln_stream_init_dispatch(const float* x, long ldx, void* s16, long lds, vo
 long vt_lstm_persistent_ws_bytes(int B, int hs);
 int vt_lstm_persistent_dispatch(LstmPersistArgs a, void* ws, long ws_bytes, hipStream_t stream);
 
+// ---- optim.hip: multi-tensor Adam / AdamW, gradient norm and clip over a chunk table
+int vt_multi_adam_dispatch(const uint64_t* table, long n_chunks, const float* hyper, float grad_coef,
+                           const float* grad_coef_dev, hipStream_t stream);
+int vt_multi_sumsq_dispatch(const uint64_t* table, long n_chunks, void* partials, hipStream_t stream);
+int vt_norm_finish_dispatch(const void* partials, long n_chunks, float max_norm, float* out, hipStream_t stream);
+int vt_multi_scale_dispatch(const uint64_t* table, long n_chunks, const float* coef_dev, hipStream_t stream);
+
 // ---- rollout.hip
 int vt_lstm_step_dispatch(const LstmStepArgs& a, hipStream_t stream);
 int vt_lstm_step_bwd_dispatch(const LstmBwdArgs& a, hipStream_t stream);

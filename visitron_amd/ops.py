@@ -915,6 +915,43 @@ def adamw_flat(p, g, m, v, p_bf16, lr, step_size, b1, b2, eps, wd, grad_scale=1.
     _lib.check(rc, "vt_adamw_flat")
 
 
+# ---- multi-tensor optimizer step, gradient norm and clip (visitron_amd/optim.py builds the tables) -------------------
+def multi_adam(table, n_chunks, hyper, grad_coef=1.0, grad_coef_dev=None, numel=0):
+    """One launch of the Adam / AdamW rule over a chunk table (int64 [n_chunks, 6] on the device: addresses of p, g, m, v,
+    element count, hyper slot).  hyper: fp32 [slots, 8] on the device.  The gradients are multiplied by the device float
+    `grad_coef_dev` where given, else by `grad_coef`.  numel: the elements the table covers (profiling only)."""
+    _require_hip(table, hyper, grad_coef_dev)
+    with _timed("multi_adam", 0.0, 28.0 * numel):
+        rc = _lib.load().vt_multi_adam(_ptr(table), int(n_chunks), _ptr(hyper), float(grad_coef), _ptr(grad_coef_dev), _stream())
+    _lib.check(rc, "vt_multi_adam")
+
+
+def multi_sumsq(table, n_chunks, partials, numel=0):
+    """partials[c] (fp64 [n_chunks]) = sum of g^2 over chunk c of the table."""
+    _require_hip(table, partials)
+    assert partials.dtype == torch.float64 and partials.numel() >= n_chunks
+    with _timed("multi_sumsq", 0.0, 4.0 * numel):
+        rc = _lib.load().vt_multi_sumsq(_ptr(table), int(n_chunks), _ptr(partials), _stream())
+    _lib.check(rc, "vt_multi_sumsq")
+
+
+def norm_finish(partials, n_chunks, max_norm, out):
+    """out (fp32 [2]) = (total_norm, clip_coef) from the per-chunk sums: torch.nn.utils.clip_grad_norm_'s rule."""
+    _require_hip(partials, out)
+    assert out.dtype == torch.float32 and out.numel() >= 2
+    with _timed("norm_finish", 0.0, 8.0 * n_chunks):
+        rc = _lib.load().vt_norm_finish(_ptr(partials), int(n_chunks), float(max_norm), _ptr(out), _stream())
+    _lib.check(rc, "vt_norm_finish")
+
+
+def multi_scale(table, n_chunks, coef_dev, numel=0):
+    """g *= coef_dev[0] over the table's gradients."""
+    _require_hip(table, coef_dev)
+    with _timed("multi_scale", 0.0, 8.0 * numel):
+        rc = _lib.load().vt_multi_scale(_ptr(table), int(n_chunks), _ptr(coef_dev), _stream())
+    _lib.check(rc, "vt_multi_scale")
+
+
 def scale_heads(x, head_scale, out=None):
     """out[r, 64 h + d] = x[r, 64 h + d] * head_scale[h] (bf16 [rows, nh * 64]; head_scale fp32 [nh])."""
     _require_hip(x, head_scale, out)
