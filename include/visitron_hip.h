@@ -78,6 +78,24 @@ int vt_gemm_shared_tile_timeouts(unsigned* host_count);
  * kernel on `stream` into the DEVICE int64 pair out2 -- for callers that read something back at that point anyway (the
  * training step's row counts): no host round trip of its own (ABI 12). */
 int vt_step_counters(int64_t* out2, vt_stream_t stream);
+/* Deterministic training mode (ABI 15).  Off (default): every launch, workspace and result is what it was before ABI 15.
+ * On: two runs of the same step on the same data give the same bits, whatever the order in which workgroups are scheduled --
+ *   - vt_attention_bwd_bf16 / vt_attention_bwd_seq_bf16 at S > 256 sum the key blocks' dQ partials in key-block order from
+ *     per-block planes instead of by fp32 atomics (layout and order: see vt_attention_bwd_bf16);
+ *   - the persistent weight-gradient kernel of vt_wgrad_bf16 (and of the encoder backward loops) adds a tile's row ranges
+ *     in row-range order instead of arrival order, its bias gradient by plain load-add-store in the same turn, and never
+ *     takes its fp32-atomic form (a launch that would need more than two row ranges per tile runs on the
+ *     one-tile-per-workgroup kernel, also under vt_debug_set_wgrad_kernel(8)).
+ * No float atomic is left on a gradient.  Process-wide (one word for all devices), read by each call when it launches: set
+ * it before a step, not between a forward and its backward.  What it does not cover: the reduction order inside a
+ * collective library, and the choice of GEMM kernel by timing, which the caller must switch off (vt_gemm_tune from a fixed
+ * table; visitron_amd.set_deterministic does both). */
+void vt_set_deterministic(int on);
+int vt_get_deterministic(void);
+/* Bytes of dq32_ws that vt_attention_bwd_bf16 / vt_attention_bwd_seq_bf16 need for this shape IN THE CURRENT MODE (rows = B*S,
+ * or the compacted row count): 0 for S <= 256; rows * nh*64 * 4 with the switch off; that times ceil(S / 256) with it on.
+ * Pure arithmetic: needs no device. */
+int64_t vt_attention_bwd_ws_bytes(int B, int S, int nh, int64_t rows);
 /* Attention-probability dropout (oscar/modeling_bert.py:62, nn.Dropout(attention_probs_dropout_prob)): how finely the drop
  * probability is resolved.  16 (default since ABI 12): steps of 1/65536 -- two neighbouring keys share one hash word, a 16-bit
  * field each -- so the reference's 0.1 runs as 6554/65536 = 0.100006.  8 (the form of ABI 8 .. 11): steps of 1/256 -- four
@@ -192,7 +210,12 @@ int vt_attention_probs_f32(const void* qkv, int64_t ld_qkv, const float* mask, i
  * pretrain.py:191).  S <= 256: no atomics, bitwise reproducible, dq32_ws may be NULL.  S > 256: the
  * keys are processed in blocks of 256 and dq is accumulated with fp32 atomics in dq32_ws, an fp32
  * [B*S, nh*64] scratch slab (zeroed here), then rounded to bf16.  keep_bits: the words the forward wrote (same
- * drop_p / seed / site), or NULL = recompute the mask from the hash. */
+ * drop_p / seed / site), or NULL = recompute the mask from the hash.
+ * Under vt_set_deterministic(1) and S > 256, dq32_ws is nkb = ceil(S / 256) PLANES of fp32 [rows, nh*64] (plane kb at float
+ * offset kb * rows * nh*64; vt_attention_bwd_ws_bytes gives the size; it need not be zeroed and is not zeroed here): plane kb
+ * receives, by plain stores, the dQ partial of keys 256 kb .. 256 kb + 255 for EVERY row of every sequence (zeros where a
+ * compacted sequence is shorter than 256 kb), and dq = bf16(((plane0 + plane1) + plane2) + ...) summed in fp32 in ascending
+ * kb.  On return the planes still hold the partials.  The caller guarantees the size: the library cannot check it. */
 int vt_attention_bwd_bf16(const void* qkv, int64_t ld_qkv, const void* dctx, int64_t ld_d, const void* ctx,
                           int64_t ld_ctx, const float* mask, int mask_additive, const float* lse,
                           float* delta_ws, void* dqkv, int64_t ld_dqkv, float* dq32_ws, int B, int S, int nh,

@@ -3,7 +3,8 @@
 Public surface = the reference's module API for this path (see ``visitron_amd.modeling``):
 ``PreTrainOscar``, ``BertImgModelwithLocationEmbeds``, ``CaptionBertEncoder`` and friends,
 ``BertConfig``, ``MODEL_CLASS``; ``set_precision(model, "fp32")`` selects the fp32 parity kernels (default: bf16);
-``check_errors()`` waits for the asynchronous error flags of the calls issued so far (ids outside an embedding table).
+``check_errors()`` waits for the asynchronous error flags of the calls issued so far (ids outside an embedding table);
+``set_deterministic(True)`` / ``is_deterministic()``: training steps that agree bit for bit from run to run.
 Arithmetic runs in ``lib/libvisitron_hip.so`` (C ABI in
 ``include/visitron_hip.h``); there is no CPU fallback.
 """
@@ -19,4 +20,8 @@ def __getattr__(name):  # lazy: importing the package must not require torch+HIP
         from . import modeling
 
         return getattr(modeling, name)
+    if name in ("set_deterministic", "is_deterministic"):   # bit-reproducible training steps (ops.set_deterministic)
+        from . import ops
+
+        return getattr(ops, name)
     raise AttributeError(name)

@@ -22,6 +22,18 @@
 // fp32 atomics into a scratch [B*S,H] slab: each slice's dQ^T is transposed through LDS so that a
 // wave-instruction adds 256 contiguous bytes of one row (the full-rate atomic shape), then a small
 // kernel rounds the slab to bf16.
+//
+// Deterministic mode (vt_set_deterministic(1); S > 256 only -- below that nothing changes).  From three key blocks on the
+// atomic sum depends on the order in which the workgroups arrive.  Under the switch the workspace is nkb = ceil(S / 256)
+// PLANES of fp32 [rows, nh*64] (rows = B*S, or the compacted row count), plane kb at float offset kb * rows * nh*64, and
+//   * the workgroup of key block kb STORES its dQ partial of every query row of its sequence into plane kb: the same
+//     256-byte-per-row wave-instruction, a plain store instead of an add.  It does so for every row below the sequence's
+//     length, also where all of its keys are masked (the partial is then 0 or tiny, but written), and a workgroup whose key
+//     block lies past a short sequence of a compacted batch stores zeros there -- so every (plane, row) is written by
+//     exactly one workgroup, nothing is zeroed beforehand and the memset is dropped;
+//   * attn_dq_round_planes forms ((p0 + p1) + p2) + ... in ascending kb in fp32 and rounds once to bf16.
+// The plane layout and this order are CONTRACT (tests/test_gpu_deterministic.py recomputes the sum from the planes).  dK and
+// dV never leave their workgroup and are the same bits in both modes.
 #include "dispatch.hpp"
 #include <type_traits>
 
@@ -53,6 +65,7 @@ struct AttnBwdArgs {
   const uint32_t* keep_bits;
   // the forward's context rows [B*S, ld_ctx] for the kernels that form delta = rowsum(dO o O) themselves (8-wave, DELTA)
   const bf16_t* ctx; long ld_ctx; float delta_mul;
+  long dq_plane;        // deterministic mode (the DET instantiations): floats per plane (rows * nh*64), key block kb stores into plane kb
 };
 
 // LDS map (bytes)
@@ -100,7 +113,17 @@ __device__ __forceinline__ void attn_bwd_keep16(const DropCfg& dr, uint32_t qbas
   }
 }
 
-__global__ __launch_bounds__(256, 1) void attention_bwd_d64(AttnBwdArgs a) {
+// Deterministic mode: a key block past a short sequence contributes nothing, and says so -- zeros in its plane for this
+// head's 64 columns of the sequence's `len` rows (one wave-instruction = one row's 256 bytes, as the partials are stored).
+__device__ __forceinline__ void attn_bwd_zero_plane_rows(float* p, int len, int H) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+  for (int q = wave; q < len; q += nwaves) p[(long)q * H + lane] = 0.f;
+}
+
+// The kernel's body.  DET: deterministic mode (several key blocks only: plane stores instead of atomics); its kernels are
+// attention_det_bwd_4w / attention_det_bwd_w8 below, the default kernels are the body with DET = false, the code as it was.
+template <bool DET>
+__device__ __forceinline__ void attn_bwd_body_4w(const AttnBwdArgs& a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -111,7 +134,10 @@ __global__ __launch_bounds__(256, 1) void attention_bwd_d64(AttnBwdArgs a) {
   const int Smax = a.S, H = a.nh * 64;
   const int S = a.seq_len ? vt_clamp_len(a.seq_len[b], a.S) : a.S;                       // this sequence's rows
   const long row0 = a.seq_start ? (long)a.seq_start[b] : (long)b * a.S;
-  if (kb0 >= S) return;                                               // uniform: a key block past a short sequence
+  if (kb0 >= S) {                                                     // uniform: a key block past a short sequence
+    if (DET) attn_bwd_zero_plane_rows(a.dq32 + blockIdx.z * a.dq_plane + row0 * H + head * 64, S, H);
+    return;
+  }
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 
   const bf16_t* base = a.qkv + row0 * a.ld_qkv + head * 64;
@@ -383,7 +409,11 @@ __global__ __launch_bounds__(256, 1) void attention_bwd_d64(AttnBwdArgs a) {
       for (int rr = 0; rr < 8; ++rr) {
         const int ql = 8 * wave + rr;
         const int q = sl * 32 + ql;
-        if (q < S) atomicAdd(a.dq32 + (row0 + q) * H + head * 64 + lane, st[ql * 64 + lane]);
+        if (q < S) {
+          float* dst = a.dq32 + (row0 + q) * H + head * 64 + lane;
+          if (DET) dst[blockIdx.z * a.dq_plane] = st[ql * 64 + lane];   // deterministic mode: plane kb, plain store
+          else atomicAdd(dst, st[ql * 64 + lane]);
+        }
       }
       // the staging tile is rewritten only after the next slice's barrier, which every wave reaches
       // after these reads
@@ -421,8 +451,12 @@ __global__ __launch_bounds__(256, 1) void attention_bwd_d64(AttnBwdArgs a) {
 // extract and two ands per element) instead of the hash (about ten vector instructions per element, a third of the loop)
 // DELTA: the row constant delta = rowsum(dO o O) (x (1-p) under dropout) is formed here, a slice ahead, from 8 bytes of dO
 // and of O per thread (16 threads per query), instead of by a separate pass over both tensors (attn_delta_rows)
-template <bool BITS, bool DELTA>
-__global__ __launch_bounds__(512, 2) void attention_bwd_d64_w8(AttnBwdArgs a) {
+__global__ __launch_bounds__(256, 1) void attention_bwd_d64(AttnBwdArgs a) { attn_bwd_body_4w<false>(a); }
+__global__ __launch_bounds__(256, 1) void attention_det_bwd_4w(AttnBwdArgs a) { attn_bwd_body_4w<true>(a); }
+
+// DET: deterministic mode, as in attn_bwd_body_4w
+template <bool BITS, bool DELTA, bool DET>
+__device__ __forceinline__ void attn_bwd_body_w8(const AttnBwdArgs& a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -433,7 +467,10 @@ __global__ __launch_bounds__(512, 2) void attention_bwd_d64_w8(AttnBwdArgs a) {
   const int Smax = a.S, H = a.nh * 64;
   const int S = a.seq_len ? vt_clamp_len(a.seq_len[b], a.S) : a.S;                       // this sequence's rows
   const long row0 = a.seq_start ? (long)a.seq_start[b] : (long)b * a.S;
-  if (kb0 >= S) return;                                               // uniform: a key block past a short sequence
+  if (kb0 >= S) {                                                     // uniform: a key block past a short sequence
+    if (DET) attn_bwd_zero_plane_rows(a.dq32 + blockIdx.z * a.dq_plane + row0 * H + head * 64, S, H);
+    return;
+  }
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 
   const bf16_t* base = a.qkv + row0 * a.ld_qkv + head * 64;
@@ -759,7 +796,11 @@ __global__ __launch_bounds__(512, 2) void attention_bwd_d64_w8(AttnBwdArgs a) {
       for (int rr = 0; rr < 4; ++rr) {
         const int ql = 4 * wave + rr;
         const int q = sl * 32 + ql;
-        if (q < S) atomicAdd(a.dq32 + (row0 + q) * H + head * 64 + lane, st[ql * 64 + lane]);
+        if (q < S) {
+          float* dst = a.dq32 + (row0 + q) * H + head * 64 + lane;
+          if (DET) dst[blockIdx.z * a.dq_plane] = st[ql * 64 + lane];   // deterministic mode: plane kb, plain store
+          else atomicAdd(dst, st[ql * 64 + lane]);
+        }
       }
       // the staging tile is rewritten only after the next slice's barrier, which every wave reaches
       // after these reads
@@ -791,6 +832,11 @@ __global__ __launch_bounds__(512, 2) void attention_bwd_d64_w8(AttnBwdArgs a) {
     }
   }
 }
+
+template <bool BITS, bool DELTA>
+__global__ __launch_bounds__(512, 2) void attention_bwd_d64_w8(AttnBwdArgs a) { attn_bwd_body_w8<BITS, DELTA, false>(a); }
+template <bool BITS, bool DELTA>
+__global__ __launch_bounds__(512, 2) void attention_det_bwd_w8(AttnBwdArgs a) { attn_bwd_body_w8<BITS, DELTA, true>(a); }
 
 // ================================================================================================
 // 16-wave form (round 4): wave w owns the 16 keys 16w .. 16w+15, every product on v_mfma_f32_16x16x32_bf16, <= 128
@@ -1472,6 +1518,34 @@ __global__ __launch_bounds__(256) void attn_dq_round(const float* __restrict__ d
   *(u32x4*)(dqkv + row * ld_dqkv + col) = o;
 }
 
+// deterministic mode: dq = round(((p0 + p1) + p2) + ...), planes in ascending key-block order, fp32, one rounding to bf16
+__global__ __launch_bounds__(256) void attn_dq_round_planes(const float* __restrict__ dq32, long plane, int nkb,
+                                                            bf16_t* __restrict__ dqkv, long ld_dqkv, long rows, int H) {
+  const int cpr = H >> 3;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows * cpr) return;
+  const long row = i / cpr;
+  const int col = (int)(i - row * cpr) * 8;
+  const float* p = dq32 + row * H + col;
+  f32x4 x0 = *(const f32x4*)p, x1 = *(const f32x4*)(p + 4);
+  for (int kb = 1; kb < nkb; ++kb) {
+    x0 += *(const f32x4*)(p + kb * plane);
+    x1 += *(const f32x4*)(p + kb * plane + 4);
+  }
+  u32x4 o;
+  o[0] = pack_bf16x2(x0[0], x0[1]); o[1] = pack_bf16x2(x0[2], x0[3]);
+  o[2] = pack_bf16x2(x1[0], x1[1]); o[3] = pack_bf16x2(x1[2], x1[3]);
+  *(u32x4*)(dqkv + row * ld_dqkv + col) = o;
+}
+
+// The dQ workspace a backward over S keys needs in the CURRENT mode, in bytes: 0 up to 256 keys (one key block, no
+// workspace), else rows * nh*64 fp32 -- one slab for the atomic sum, ceil(S / 256) planes under vt_set_deterministic(1).
+long vt_attention_bwd_ws_bytes_impl(int B, int S, int nh, long rows) {
+  if (B <= 0 || S <= 256 || nh <= 0 || rows <= 0) return 0;
+  const long slab = rows * nh * 64 * (long)sizeof(float);
+  return vt_deterministic() ? slab * ((S + 255) / 256) : slab;
+}
+
 // 8 (default): the 8-wave kernel forming delta = rowsum(dO o O) itself; 10: the same kernel behind a separate
 // attn_delta_rows pass (the form before round 3's last change: 330-338 against 320 us per launch at B = 256); 4: the 4-wave kernel
 // 16 (default): the 16-wave kernel where it serves (one key block, no per-query bias, keep words or no dropout), else as 8
@@ -1493,8 +1567,9 @@ int vt_attention_bwd_dispatch(const void* qkv, long ld_qkv, const void* dctx, lo
   if (B <= 0 || S <= 0 || nh <= 0 || B > 65535 || nh > 65535) return VT_ERR_BAD_SHAPE;
   if ((ld_qkv % 8) || (ld_d % 8) || (ld_ctx % 8) || (ld_dqkv % 8)) return VT_ERR_BAD_ALIGN;
   if (((uintptr_t)qkv | (uintptr_t)dctx | (uintptr_t)ctx | (uintptr_t)dqkv) & 15) return VT_ERR_BAD_ALIGN;
-  static VtLdsAttrOnce attr4;
+  static VtLdsAttrOnce attr4, attr4d;
   if (!attr4.set((const void*)attention_bwd_d64, AB_LDS_BYTES)) return VT_ERR_HIP;
+  if (!attr4d.set((const void*)attention_det_bwd_4w, AB_LDS_BYTES)) return VT_ERR_HIP;
   if ((seq_start == nullptr) != (seq_len == nullptr)) return VT_ERR_NULL;
   if (seq_start && (mask || rows_total <= 0)) return VT_ERR_UNSUPPORTED;   // compacted rows carry no masked keys
   const long rows = seq_start ? rows_total : (long)B * S;
@@ -1507,7 +1582,10 @@ int vt_attention_bwd_dispatch(const void* qkv, long ld_qkv, const void* dctx, lo
   a.qkv = (const bf16_t*)qkv; a.dctx = (const bf16_t*)dctx; a.mask = mask; a.mask_additive = mask_additive;
   a.lse = lse; a.delta = delta_ws; a.dqkv = (bf16_t*)dqkv;
   a.dq32 = nkb > 1 ? dq32_ws : nullptr;
-  if (nkb > 1 && hipMemsetAsync(dq32_ws, 0, (size_t)rows * nh * 64 * sizeof(float), stream) != hipSuccess) return VT_ERR_HIP;
+  // deterministic mode: one plane per key block, every (plane, row) stored by exactly one workgroup -- nothing to zero
+  const bool det = nkb > 1 && vt_deterministic();
+  a.dq_plane = det ? rows * nh * 64 : 0;
+  if (nkb > 1 && !det && hipMemsetAsync(dq32_ws, 0, (size_t)rows * nh * 64 * sizeof(float), stream) != hipSuccess) return VT_ERR_HIP;
   a.ld_qkv = ld_qkv; a.ld_d = ld_d; a.ld_dqkv = ld_dqkv; a.B = B; a.S = S; a.nh = nh;
   a.seq_start = seq_start; a.seq_len = seq_len;
   a.scale = 1.0f / sqrtf((float)head_size);
@@ -1531,7 +1609,8 @@ int vt_attention_bwd_dispatch(const void* qkv, long ld_qkv, const void* dctx, lo
     if (a.keep_bits) hipLaunchKernelGGL((attention_bwd_d64_w16<true>), dim3(nh, B), dim3(1024), AW_LDS_BYTES, stream, a);
     else hipLaunchKernelGGL((attention_bwd_d64_w16<false>), dim3(nh, B), dim3(1024), AW_LDS_BYTES, stream, a);
   } else if (g_attn_bwd_waves == 4) {
-    hipLaunchKernelGGL(attention_bwd_d64, dim3(nh, B, nkb), dim3(256), AB_LDS_BYTES, stream, a);
+    if (det) hipLaunchKernelGGL(attention_det_bwd_4w, dim3(nh, B, nkb), dim3(256), AB_LDS_BYTES, stream, a);
+    else hipLaunchKernelGGL(attention_bwd_d64, dim3(nh, B, nkb), dim3(256), AB_LDS_BYTES, stream, a);
   } else {
     static VtLdsAttrOnce attr8, attr8b, attr8d, attr8bd;
     if (!attr8.set((const void*)attention_bwd_d64_w8<false, false>, AB_LDS_BYTES)) return VT_ERR_HIP;
@@ -1539,7 +1618,18 @@ int vt_attention_bwd_dispatch(const void* qkv, long ld_qkv, const void* dctx, lo
     if (!attr8d.set((const void*)attention_bwd_d64_w8<false, true>, AB_LDS_BYTES)) return VT_ERR_HIP;
     if (!attr8bd.set((const void*)attention_bwd_d64_w8<true, true>, AB_LDS_BYTES)) return VT_ERR_HIP;
     const dim3 grid(nh, B, nkb);
-    if (g_attn_bwd_waves == 8 || g_attn_bwd_waves >= 16) {
+    if (det) {   // the same four forms with the plane stores
+      static VtLdsAttrOnce attr8x[4];
+      const void* kd[4] = {(const void*)attention_det_bwd_w8<false, false>, (const void*)attention_det_bwd_w8<true, false>,
+                           (const void*)attention_det_bwd_w8<false, true>, (const void*)attention_det_bwd_w8<true, true>};
+      for (int i = 0; i < 4; ++i)
+        if (!attr8x[i].set(kd[i], AB_LDS_BYTES)) return VT_ERR_HIP;
+      const bool delta = g_attn_bwd_waves == 8 || g_attn_bwd_waves >= 16;
+      if (delta && a.keep_bits) hipLaunchKernelGGL((attention_det_bwd_w8<true, true>), grid, dim3(512), AB_LDS_BYTES, stream, a);
+      else if (delta) hipLaunchKernelGGL((attention_det_bwd_w8<false, true>), grid, dim3(512), AB_LDS_BYTES, stream, a);
+      else if (a.keep_bits) hipLaunchKernelGGL((attention_det_bwd_w8<true, false>), grid, dim3(512), AB_LDS_BYTES, stream, a);
+      else hipLaunchKernelGGL((attention_det_bwd_w8<false, false>), grid, dim3(512), AB_LDS_BYTES, stream, a);
+    } else if (g_attn_bwd_waves == 8 || g_attn_bwd_waves >= 16) {
       if (a.keep_bits) hipLaunchKernelGGL((attention_bwd_d64_w8<true, true>), grid, dim3(512), AB_LDS_BYTES, stream, a);
       else hipLaunchKernelGGL((attention_bwd_d64_w8<false, true>), grid, dim3(512), AB_LDS_BYTES, stream, a);
     } else {
@@ -1549,8 +1639,10 @@ int vt_attention_bwd_dispatch(const void* qkv, long ld_qkv, const void* dctx, lo
   }
   if (nkb > 1) {
     const long n = rows * (nh * 8);
-    hipLaunchKernelGGL(attn_dq_round, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, dq32_ws, (bf16_t*)dqkv, ld_dqkv,
-                       rows, nh * 64);
+    if (det) hipLaunchKernelGGL(attn_dq_round_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, dq32_ws, a.dq_plane,
+                                nkb, (bf16_t*)dqkv, ld_dqkv, rows, nh * 64);
+    else hipLaunchKernelGGL(attn_dq_round, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, dq32_ws, (bf16_t*)dqkv, ld_dqkv,
+                            rows, nh * 64);
   }
   return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
 }

@@ -22,7 +22,12 @@ const char* vt_error_string(int code) {
   }
 }
 
-int vt_abi_version(void) { return 14; }
+int vt_abi_version(void) { return 15; }
+
+// deterministic training mode (common.hpp): one word for the process, read by every dispatch at launch time
+void vt_set_deterministic(int on) { vt_deterministic_word().store(on ? 1 : 0, std::memory_order_relaxed); }
+int vt_get_deterministic(void) { return vt_deterministic() ? 1 : 0; }
+int64_t vt_attention_bwd_ws_bytes(int B, int S, int nh, int64_t rows) { return vt_attention_bwd_ws_bytes_impl(B, S, nh, (long)rows); }
 
 // attention-probability dropout: 16-bit fields (default since ABI 12: p in steps of 1/65536, two keys per hash word -- the
 // reference's nn.Dropout(0.1) runs as 0.100006) or 8-bit fields (rounds 4-5's form: steps of 1/256, four keys per hash word,

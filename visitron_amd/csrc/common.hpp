@@ -398,6 +398,15 @@ struct VtLdsAttrOnce {
     return true;
   }
 };
+// Deterministic training mode (vt_set_deterministic): fixed-order dQ and dW sums, no float atomics.  Like the state above it
+// is host-side, behind an atomic and read by each dispatch when it launches; unlike it, ONE word serves every device -- the
+// mode belongs to the run (all replicas of a DataParallel step must agree on it), and it must be settable and readable in a
+// process that has no device at all (sizing a workspace ahead of time).
+inline std::atomic<int>& vt_deterministic_word() {
+  static std::atomic<int> on{0};
+  return on;
+}
+inline bool vt_deterministic() { return vt_deterministic_word().load(std::memory_order_relaxed) != 0; }
 
 // error codes of the C ABI (include/visitron_hip.h)
 #define VT_OK 0

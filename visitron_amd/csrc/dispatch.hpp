@@ -27,6 +27,9 @@ int vt_attention_bwd_dispatch(const void* qkv, long ld_qkv, const void* dctx, lo
                               long ld_dqkv, float* dq32_ws, int B, int S, int nh, int head_size, hipStream_t stream,
                               const DropCfg* drop = nullptr, const int* seq_start = nullptr, const int* seq_len = nullptr,
                               long rows_total = 0, const uint32_t* keep_bits = nullptr);
+// deterministic mode (the switch itself: vt_deterministic() / vt_deterministic_word() in common.hpp, set by capi.hip's
+// vt_set_deterministic): bytes of dq32_ws the backward needs in the current mode, 0 where it needs none
+long vt_attention_bwd_ws_bytes_impl(int B, int S, int nh, long rows);
 
 // ---- attention_fwd.hip
 int vt_attention_fwd_dispatch(const void* qkv, long ld_qkv, const float* mask, int mask_additive, const float* head_scale, void* ctx,

@@ -19,6 +19,7 @@ struct WgradArgs {
   WgradProblem p[WG_MAX_PROBLEMS];
   int nprob;
   int M;
+  int det;   // deterministic mode, filled by vt_wgrad_v8_dispatch at launch (the persistent kernel's turn order); others ignore it
 };
 
 int vt_wgrad_v8_dispatch(WgradArgs& a, hipStream_t stream, bool force);   // gemm_wgrad_v8.hip, called from vt_wgrad_dispatch

@@ -300,7 +300,29 @@ def multi_rank_gemm_policy(environ=None):
     return 0, ("persistent GEMM off beside the collective (default; VT_GEMM_RESERVE_CUS=k opts into the persistent kernels on "
                "CUs - k): one-tile-per-workgroup kernels")
 _tuned = {}
+_timed_keys = set()   # keys of _tuned whose variant came out of timing launches (deterministic mode re-registers those)
 _forced_variant = None
+
+
+def set_deterministic(flag):
+    """Process-wide switch (include/visitron_hip.h, vt_set_deterministic): with it on two runs of the same training step on
+    the same data agree bit for bit.  The attention backward over more than 256 keys sums its key blocks' dQ partials from
+    planes in key-block order, the persistent weight-gradient kernel adds a tile's row ranges in row-range order and its
+    bias gradient without atomics, and the GEMM kernel of a shape no longer depends on timing: autotune_linear takes
+    VT_TUNE_FILE or the committed gemm_defaults.json, as under VT_AUTOTUNE=0, and launches nothing.  Read by every call
+    when it launches (nothing caches it): set it before a step, not between a forward and its backward.  Off (default):
+    every launch, workspace and result as without the switch.  Not covered: the reduction order inside RCCL."""
+    _lib.load().vt_set_deterministic(1 if flag else 0)
+
+
+def is_deterministic():
+    return bool(_lib.load().vt_get_deterministic())
+
+
+def attention_bwd_ws_bytes(B, S, nh, rows=None):
+    """Bytes of the dq32 workspace attention_bwd needs for this shape in the current mode (rows: the compacted row count,
+    default B * S): 0 up to 256 keys, rows * nh * 64 * 4 beyond, times ceil(S / 256) under set_deterministic(True)."""
+    return int(_lib.load().vt_attention_bwd_ws_bytes(int(B), int(S), int(nh), int(B * S if rows is None else rows)))
 
 
 def force_gemm_variant(v):
@@ -365,7 +387,8 @@ def autotune_linear(M, N, K, act=ACT_NONE, residual=False, pre_act=False, device
     key = (M, N, K, kind)
     if _forced_variant is not None:
         return _forced_variant
-    if key in _tuned:
+    det = is_deterministic()
+    if key in _tuned and not (det and key in _timed_keys):
         return _tuned[key]
     lib = _lib.load()
     have_ws = ensure_gemm_workspace(device)   # (before any variant is registered: SHARED_TILE_VARIANTS need it at launch time)
@@ -381,10 +404,17 @@ def autotune_linear(M, N, K, act=ACT_NONE, residual=False, pre_act=False, device
         _tuned[key] = int(saved)
         return _tuned[key]
     default = _default_variant(key)
-    if os.environ.get("VT_AUTOTUNE", "1") == "0" and usable(default):
+    if (det or os.environ.get("VT_AUTOTUNE", "1") == "0") and usable(default):
         lib.vt_gemm_tune(M, N, K, kind, int(default))
         _tuned[key] = int(default)
+        _timed_keys.discard(key)
         return _tuned[key]
+    if det:
+        # no committed choice for this (N, K, epilogue) near M: nothing is registered and the library takes its built-in
+        # choice, a function of the shape and of the entries registered so far.  (A choice that timing registered for this
+        # very key while the switch was off cannot be withdrawn from the library's table and stays: for two PROCESSES to
+        # agree, set the switch before the first step.)
+        return _tuned.get(key)
     g = torch.Generator(device=device).manual_seed(M + N + K)   # on the device: a CPU draw of M x 3072 values costs seconds
     a = torch.randn(M, K, generator=g, device=device).to(BF16)
     w = (torch.randn(N, K, generator=g, device=device) * 0.03).to(BF16)
@@ -447,6 +477,7 @@ def autotune_linear(M, N, K, act=ACT_NONE, residual=False, pre_act=False, device
                 " ".join("%.1f" % (t * 1e3) for t in times[v]), "  <- chosen" if v == best else ""))
     lib.vt_gemm_tune(M, N, K, kind, best)
     _tuned[key] = best
+    _timed_keys.add(key)
     _tune_file_store(key, best)
     return best
 
@@ -713,8 +744,18 @@ def attention_bwd(qkv, dctx, ctx, lse, B, S, nh, mask=None, mask_additive=False,
         out = torch.empty((nrows, 3 * H), dtype=BF16, device=qkv.device)
     if delta_ws is None:
         delta_ws = torch.empty((B, nh, S), dtype=torch.float32, device=qkv.device)
-    if dq32_ws is None and S > 256:
-        dq32_ws = torch.empty((nrows, H), dtype=torch.float32, device=qkv.device)
+    # the dQ workspace of the current mode (one fp32 slab; under set_deterministic one plane per key block): the library's
+    # own figure, and a caller's buffer that is smaller is refused here -- the kernels cannot check it
+    need = attention_bwd_ws_bytes(B, S, nh, nrows)
+    if dq32_ws is None and need:
+        dq32_ws = torch.empty(need // 4, dtype=torch.float32, device=qkv.device)
+    if need:
+        _require_hip(dq32_ws)
+        if dq32_ws.dtype != torch.float32 or not dq32_ws.is_contiguous() or dq32_ws.numel() * 4 < need:
+            raise ValueError("attention_bwd: dq32_ws must be a contiguous fp32 tensor of at least %d bytes for B=%d S=%d nh=%d "
+                             "rows=%d (deterministic mode %s), got %s of %d bytes" % (
+                                 need, B, S, nh, nrows, "on" if is_deterministic() else "off", dq32_ws.dtype,
+                                 dq32_ws.numel() * dq32_ws.element_size()))
     if seq is not None:
         assert mask is None and seq.B == B and seq.S == S
         with _timed("attention_bwd_d64", 10.0 * B * nh * S * S * 64, 2.0 * nrows * 9 * H):

@@ -153,8 +153,10 @@ class _TrainBuffers(object):
                          g_pre_d=mk(H), g_pre2_d=mk(H),   # dropout-masked copies (hidden dropout > 0)
                          delta=torch.empty((B, nh, S), dtype=torch.float32, device=dev),
                          ln_partial=torch.empty(ops.LN_BWD_WS_ROWS * 2 * H, dtype=torch.float32, device=dev))
-        if S > 256:  # attention backward over several key blocks accumulates dQ in fp32
-            self.ws_t["dq32"] = torch.empty((M, H), dtype=torch.float32, device=dev)
+        self._dq32_shape = (B, S, nh, M)
+        need = ops.attention_bwd_ws_bytes(B, S, nh, M)
+        if need:  # attention backward over several key blocks: dQ in fp32 (one slab; one plane per key block when deterministic)
+            self.ws_t["dq32"] = torch.empty(need // 4, dtype=torch.float32, device=dev)
         self.ws = _lib.BwdWorkspace()
         for k, v in self.ws_t.items():
             setattr(self.ws, k, v.data_ptr())
@@ -166,6 +168,22 @@ class _TrainBuffers(object):
         self.ws_b = _lib.BwdWorkspace()
         for k, v in self.ws_t_b.items():
             setattr(self.ws_b, k, v.data_ptr())
+
+
+def _fit_dq32(self):
+    """The dQ workspace follows ops.set_deterministic: called in front of every backward, it asks the library what the current
+    mode needs and grows the buffer (both workspace tables point at it) when the switch was turned on after the buffers
+    were built."""
+    need = ops.attention_bwd_ws_bytes(*self._dq32_shape)
+    have = self.ws_t.get("dq32")
+    if need and (have is None or have.numel() * 4 < need):
+        buf = torch.empty(need // 4, dtype=torch.float32, device=self.x0.device)
+        for tab, ws in ((self.ws_t, self.ws), (self.ws_t_b, self.ws_b)):
+            tab["dq32"] = buf
+            ws.dq32 = buf.data_ptr()
+
+
+_TrainBuffers.fit_dq32 = _fit_dq32
 
 
 def _ctx_raw(self, layer):
@@ -400,9 +418,14 @@ class PretrainEngine(object):
                     _lib.load().vt_gemm_reserve_cus(k)
                 else:
                     ops.PERSISTENT_GEMM_OK = False
-            ops.autotune_encoder_shapes(B * S, cfg.hidden_size, cfg.intermediate_size, training=True,
-                                        device=self.flat.p.device)
             self._bufs[key] = b
+        # GEMM choices of the padded row count, once per mode: under ops.set_deterministic they come from the committed table
+        # (no timing launches), so a switch turned on later re-registers them
+        tkey = ("padded", B * S, ops.is_deterministic())
+        if tkey not in self._tuned_rows:
+            ops.autotune_encoder_shapes(B * S, self.cfg.hidden_size, self.cfg.intermediate_size, training=True,
+                                        device=self.flat.p.device)
+            self._tuned_rows.add(tkey)
         return b
 
     # ------------------------------------------------------------------------------ schedule
@@ -502,6 +525,7 @@ class PretrainEngine(object):
                                "launch; that step's activations / gradients are unreliable" % late)
         Ml, Mt = (int(vals[1]), int(vals[2])) if labels is not None else (0, 0)
         compact = try_compact and int(vals[3]) < M and not vals[4]
+        det = ops.is_deterministic()   # read per step (the tuned-shape keys below carry it: a later switch re-registers)
         lay = None
         if labels is not None or compact:   # one launch: the supervised-row lists and the compacted layout
             idx_w, idx_t, lay = ops.batch_row_lists(lab, tl, cmask if compact else None, B, S, Ml, Mt, int(vals[3]), tiles)
@@ -516,17 +540,17 @@ class PretrainEngine(object):
             # 1 791 tiles = 7.00 rounds against 1 800 = 7.03, i.e. eight).  profiles/r06/tune_bucket_ab.txt: +1.9 % / +0.6 %.
             bucket = round_up(Mr, int(os.environ.get("VT_TUNE_BUCKET_LARGE", "256")) if Mr >= 16384
                               else int(os.environ.get("VT_TUNE_BUCKET_SMALL", "512")))
-            if bucket not in self._tuned_rows and bucket < M:
+            if (bucket, det) not in self._tuned_rows and bucket < M:
                 ops.autotune_encoder_shapes(bucket, H, I, training=True, device=dev)
-                self._tuned_rows.add(bucket)
+                self._tuned_rows.add((bucket, det))
         # the MLM head's two wide GEMMs ([Ml, 768] x [768, 30528] and back) are tuned like the encoder's, once per bucket of
         # 512 supervised rows (the row count changes from batch to batch; the library takes the nearest tuned M)
         if Ml:
             hb = round_up(Ml, 512)
-            if ("head", hb) not in self._tuned_rows:
+            if ("head", hb, det) not in self._tuned_rows:
                 ops.autotune_linear(hb, self.Vp, H, device=dev, out_f32=True)
                 ops.autotune_linear(hb, H, self.Vp, device=dev)
-                self._tuned_rows.add(("head", hb))
+                self._tuned_rows.add(("head", hb, det))
         rows_w = rows_t = None
         if labels is not None:   # supervised rows in the layout in use
             rows_w = idx_w if lay is None else lay.inverse.index_select(0, idx_w)
@@ -746,6 +770,7 @@ class PretrainEngine(object):
         g = bufs.g[:Mr]
         if g32 is not None:
             g.copy_(g32)
+        bufs.fit_dq32()   # (the deterministic switch is read here, per backward: no copy of it is kept)
         if d_hidden is not None and comm is not None:
             raise NotImplementedError("gradients of intermediate hidden states together with the chunked data-parallel backward")
         if ops.profiling() or hs is not None:
@@ -1028,7 +1053,7 @@ class PretrainEngine(object):
                                    mask_additive=False, hs=None, inject=None):
         cfg = self.cfg
         nh, eps, M = cfg.num_attention_heads, cfg.layer_norm_eps, x0.shape[0]
-        rowed = ("g_pre", "g_pre2", "g_mid", "g_ctx", "g_qkv", "g_pre_d", "g_pre2_d", "dq32")
+        rowed = ("g_pre", "g_pre2", "g_mid", "g_ctx", "g_qkv", "g_pre_d", "g_pre2_d")
         w = {k: (v[:M] if k in rowed else v) for k, v in bufs.ws_t.items()}
         for l in range(cfg.num_hidden_layers - 1, -1, -1):
             if inject is not None and l + 1 < cfg.num_hidden_layers and inject[l + 1] is not None:
@@ -1163,7 +1188,9 @@ class PretrainEngine(object):
                                grad_comm_dtype=self.grad_comm_dtype, world_size=self.world, precision=self.precision,
                                hidden_dropout=float(self.cfg.hidden_dropout_prob),
                                attention_dropout_configured=float(self.cfg.attention_probs_dropout_prob),
-                               attention_dropout_effective=self.attention_dropout_effective))
+                               attention_dropout_effective=self.attention_dropout_effective,
+                               # ops.set_deterministic at the time of the call (recorded, not restored: a process-wide switch)
+                               deterministic=ops.is_deterministic()))
 
     def load_state_dict(self, sd, load_hyper=True):
         f = self.flat
