@@ -552,6 +552,18 @@ int vt_linear_f32(const float* a, int64_t lda, const float* w, int64_t ldw, int 
 int vt_bmm_f32(const float* a, int64_t lda, int64_t a_stride_b, int64_t a_stride_h, const float* w, int64_t ldw,
                int64_t w_stride_b, int64_t w_stride_h, int w_is_kn, float* out, int64_t ldc, int64_t c_stride_b,
                int64_t c_stride_h, int M, int N, int K, float alpha, int batch, int heads, vt_stream_t stream);
+/* vt_linear_bf16x3 / vt_bmm_bf16x3 (ABI 16): vt_linear_f32 / vt_bmm_f32 -- the same fp32 operands, arguments, epilogue and
+ * fp32 output -- with the product on the bf16 matrix cores: each fp32 element is split in the kernel into hi = bf16(x) and
+ * lo = bf16(x - hi) (round to nearest even) and a . w is formed as lo.hi + hi.lo + hi.hi with fp32 accumulation, so
+ * |error| <= 3 * 2^-16 * |alpha| * sum_k |a||w| to first order, plus the fp32 accumulation's own.  Nothing is cached between
+ * calls.  An inf / NaN operand element may turn the outputs it reaches into NaN; finite operands inside bf16's range never
+ * produce a non-finite result on their own. */
+int vt_linear_bf16x3(const float* a, int64_t lda, const float* w, int64_t ldw, int w_is_kn, const float* bias,
+                     const float* residual, int64_t ldr, float* out, int64_t ldc, int M, int N, int K, int act, float alpha,
+                     int grp_rows, int grp_stride, vt_stream_t stream);
+int vt_bmm_bf16x3(const float* a, int64_t lda, int64_t a_stride_b, int64_t a_stride_h, const float* w, int64_t ldw,
+                  int64_t w_stride_b, int64_t w_stride_h, int w_is_kn, float* out, int64_t ldc, int64_t c_stride_b,
+                  int64_t c_stride_h, int M, int N, int K, float alpha, int batch, int heads, vt_stream_t stream);
 /* In place on x [rows, cols] fp32: x * scale + mask -> Softmax(dim=-1) -> * head_scale (oscar/modeling_bert.py:53-66).
  * Row r = (b * nh + h) * S + q.  mask_mode: -1 none; 0 raw mask [B, cols] -> (1 - m) * -10000 (encoder.py:238-241);
  * 1 additive [B, cols]; 2 additive per query [B, S, cols].  With nh = S = 1 and no mask: a plain row softmax (the token

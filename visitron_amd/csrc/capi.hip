@@ -22,7 +22,7 @@ const char* vt_error_string(int code) {
   }
 }
 
-int vt_abi_version(void) { return 15; }
+int vt_abi_version(void) { return 16; }
 
 // deterministic training mode (common.hpp): one word for the process, read by every dispatch at launch time
 void vt_set_deterministic(int on) { vt_deterministic_word().store(on ? 1 : 0, std::memory_order_relaxed); }
@@ -506,6 +506,21 @@ int vt_bmm_f32(const float* a, int64_t lda, int64_t a_stride_b, int64_t a_stride
   return vt_gemm_f32_dispatch(a, lda, a_stride_b, a_stride_h, w, ldw, w_stride_b, w_stride_h, w_is_kn, nullptr, nullptr, 0,
                               out, ldc, c_stride_b, c_stride_h, M, N, K, VT_ACT_NONE, alpha, batch, heads, 0, 0,
                               (hipStream_t)stream);
+}
+
+int vt_linear_bf16x3(const float* a, int64_t lda, const float* w, int64_t ldw, int w_is_kn, const float* bias,
+                     const float* residual, int64_t ldr, float* out, int64_t ldc, int M, int N, int K, int act, float alpha,
+                     int grp_rows, int grp_stride, vt_stream_t stream) {
+  return vt_gemm_bf16x3_dispatch(a, lda, 0, 0, w, ldw, 0, 0, w_is_kn, bias, residual, ldr, out, ldc, 0, 0, M, N, K, act, alpha,
+                                 1, 1, grp_rows, grp_stride, (hipStream_t)stream);
+}
+
+int vt_bmm_bf16x3(const float* a, int64_t lda, int64_t a_stride_b, int64_t a_stride_h, const float* w, int64_t ldw,
+                  int64_t w_stride_b, int64_t w_stride_h, int w_is_kn, float* out, int64_t ldc, int64_t c_stride_b,
+                  int64_t c_stride_h, int M, int N, int K, float alpha, int batch, int heads, vt_stream_t stream) {
+  return vt_gemm_bf16x3_dispatch(a, lda, a_stride_b, a_stride_h, w, ldw, w_stride_b, w_stride_h, w_is_kn, nullptr, nullptr, 0,
+                                 out, ldc, c_stride_b, c_stride_h, M, N, K, VT_ACT_NONE, alpha, batch, heads, 0, 0,
+                                 (hipStream_t)stream);
 }
 
 int vt_softmax_rows_f32(float* x, int64_t ld, int64_t rows, int cols, float scale, const float* mask, int mask_mode,

@@ -73,6 +73,12 @@ int vt_embed_layernorm_f32_dispatch(const int64_t* ids, const int64_t* type_ids,
                                     long ldy, int B, int T, int S, int H, int n_word, int n_pos, int n_type, float eps,
                                     int* err_flag, hipStream_t stream);
 
+// ---- bf16x3_path.hip: the fp32 route's products as three bf16 MFMAs per term pair (arguments as vt_gemm_f32_dispatch)
+int vt_gemm_bf16x3_dispatch(const float* A, long lda, long sA_b, long sA_h, const float* W, long ldw, long sW_b, long sW_h,
+                            int w_is_kn, const float* bias, const float* R, long ldr, float* C, long ldc, long sC_b, long sC_h,
+                            int M, int N, int K, int act, float alpha, int batch, int heads, int grp_rows, int grp_stride,
+                            hipStream_t stream);
+
 // ---- fp32_train.hip: what only the fp32 training step runs
 int vt_colsum_f32_dispatch(const float* x, long ldx, long rows, int cols, float* out, int accumulate, float* ws,
                            hipStream_t stream);

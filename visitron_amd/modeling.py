@@ -597,15 +597,25 @@ def invalidate_packed_weights():
     _WEIGHTS_GEN[0] += 1
 
 
-PRECISIONS = ("bf16", "fp32")
+PRECISIONS = ("bf16", "fp32", "bf16x3")
 
 
 def set_precision(model, precision):
-    """Select the arithmetic of `model`'s HIP forward: "bf16" (default: bf16 operands on the bf16 matrix cores, fp32
-    accumulation -- the performance path, within 5e-2 of the fp32 reference) or "fp32" (every operand, activation and
-    accumulation in fp32 on the fp32 matrix cores -- the parity path, within 1e-3 of the reference, which computes in
-    fp32 itself: tasks/viewpoint_select/encoder.py:238-240).  "fp32" serves inference at encoder / trunk / model level;
-    training stays on the bf16 kernels."""
+    """Select the arithmetic of `model`'s HIP forward:
+
+    "bf16" (default)  bf16 operands on the bf16 matrix cores, fp32 accumulation -- the performance path, within 5e-2 of the
+                      fp32 reference.
+    "fp32"            every operand, activation and accumulation in fp32 on the fp32 matrix cores -- the parity path, within
+                      1e-3 of the reference (1e-5 measured), which computes in fp32 itself
+                      (tasks/viewpoint_select/encoder.py:238-240).
+    "bf16x3"          the fp32 route with every matrix product (nn.Linear and the two attention products) on the bf16 matrix
+                      cores: each fp32 operand is split in the kernel into two bf16 terms and the product formed from three
+                      bf16 MFMAs with fp32 accumulation (csrc/bf16x3_path.hip), 16 significant bits per operand.  Embeddings,
+                      LayerNorm, softmax, the literal mask bias and the losses are the fp32 route's own.  Within 1e-3 of the
+                      reference (2e-4 measured).
+
+    "fp32" and "bf16x3" serve inference at encoder / trunk / model level; training stays on the bf16 kernels (or
+    PretrainEngine(precision="fp32"))."""
     if precision not in PRECISIONS:
         raise ValueError("precision must be one of %s" % (PRECISIONS,))
     for m in model.modules():
@@ -614,7 +624,13 @@ def set_precision(model, precision):
 
 
 def _is_fp32(module):
-    return getattr(module, "_vt_precision", "bf16") == "fp32"
+    """Does this module take the fp32 route (fp32 activations, run_f32)?  True under "fp32" and under "bf16x3"."""
+    return getattr(module, "_vt_precision", "bf16") in ("fp32", "bf16x3")
+
+
+def _products(module):
+    """The product arithmetic of a module on the fp32 route (ops.linear_f32 / ops.attention_f32's `products`)."""
+    return "bf16x3" if getattr(module, "_vt_precision", "bf16") == "bf16x3" else "fp32"
 
 
 def _param_key(module_or_params):
@@ -879,14 +895,16 @@ class CaptionBertEncoder(nn.Module):
         return ws["outs"]
 
     def run_f32(self, x, B, S, mask_f32, mask_additive, head_scale=None, history=None):
-        """The layer loop in fp32 (set_precision(model, "fp32")): x fp32 [B*S, H] -> list of the L layer outputs (fp32);
-        per-layer attention probabilities land in self._last_attentions when output_attentions is set."""
+        """The layer loop in fp32 (set_precision(model, "fp32") or "bf16x3": the module's choice decides the arithmetic of the
+        products, nothing else): x fp32 [B*S, H] -> list of the L layer outputs (fp32); per-layer attention probabilities land
+        in self._last_attentions when output_attentions is set."""
         if self._hidden != self._heads * 64:
             raise NotImplementedError("the fp32 path serves head size 64 (hidden = 64 * heads)")
         nh, H, eps = self._heads, self._hidden, self._eps
         probs_all = [] if self.output_attentions else None
         outs, cur = [], x
         f = _f32
+        pr = _products(self)
         for i, layer in enumerate(self.layer):
             att, so = layer.attention.self, layer.attention.output
             w_qkv = torch.cat([att.query.weight, att.key.weight, att.value.weight], 0).detach().float().contiguous()
@@ -897,19 +915,20 @@ class CaptionBertEncoder(nn.Module):
                 Sh = history[i].shape[1]
                 xs = torch.cat([history[i].detach().float(), cur.view(B, S, H)], 1).reshape(B * (Sh + S), H).contiguous()
             St = Sh + S
-            qkv = ops.linear_f32(xs, w_qkv, b_qkv)
+            qkv = ops.linear_f32(xs, w_qkv, b_qkv, products=pr)
             ctx, p_i = ops.attention_f32(qkv, B, St, nh, mask=mask_f32, mask_additive=mask_additive, head_scale=hs_i,
-                                         want_probs=probs_all is not None)
+                                         want_probs=probs_all is not None, products=pr)
             if Sh:
                 ctx = ctx.view(B, St, H)[:, Sh:].reshape(B * S, H).contiguous()
                 if p_i is not None:
                     p_i = p_i[:, :, Sh:, :].contiguous()
             if probs_all is not None:
                 probs_all.append(p_i)
-            pre = ops.linear_f32(ctx, f(so.dense.weight), f(so.dense.bias), residual=cur)
+            pre = ops.linear_f32(ctx, f(so.dense.weight), f(so.dense.bias), residual=cur, products=pr)
             a_out = ops.layernorm_rows(pre, f(so.LayerNorm.weight), f(so.LayerNorm.bias), eps)
-            mid = ops.linear_f32(a_out, f(layer.intermediate.dense.weight), f(layer.intermediate.dense.bias), act=ACT_GELU)
-            pre2 = ops.linear_f32(mid, f(layer.output.dense.weight), f(layer.output.dense.bias), residual=a_out)
+            mid = ops.linear_f32(a_out, f(layer.intermediate.dense.weight), f(layer.intermediate.dense.bias), act=ACT_GELU,
+                                 products=pr)
+            pre2 = ops.linear_f32(mid, f(layer.output.dense.weight), f(layer.output.dense.bias), residual=a_out, products=pr)
             cur = ops.layernorm_rows(pre2, f(layer.output.LayerNorm.weight), f(layer.output.LayerNorm.bias), eps)
             outs.append(cur)
         self._last_attentions = probs_all
@@ -1145,14 +1164,14 @@ class BertImgModelwithLocationEmbeds(BertPreTrainedModel):
             a = torch.cat([img_feats.reshape(B * R, -1).float(), img_location_embeddings.reshape(B * R, -1).float()], 1)
             w = torch.cat([_f32(self.img_embedding.weight), _f32(self.location_embeds.weight)], 1).contiguous()
             b = _f32(self.img_embedding.bias) + _f32(self.location_embeds.bias)
-            ops.linear_f32(a.contiguous(), w, b, out=x[T:], ldc=H, grp_rows=R, grp_stride=S)
+            ops.linear_f32(a.contiguous(), w, b, out=x[T:], ldc=H, grp_rows=R, grp_stride=S, products=_products(self))
             if self.use_img_layernorm:
                 ops.layernorm_rows(x[T:], _f32(self.LayerNorm.weight), _f32(self.LayerNorm.bias),
                                    self.LayerNorm.variance_epsilon, out=x[T:], M=B * R, grp_rows=R, grp_stride=S)
         self._last_layout = None
         outs = self.encoder.run_f32(x, B, S, mask_f32, mask_is_additive, hs, history=history)
         pooled = ops.linear_f32(outs[-1], _f32(self.pooler.dense.weight), _f32(self.pooler.dense.bias), act=ACT_TANH,
-                                M=B, lda=S * H)
+                                M=B, lda=S * H, products=_products(self))
         _check_index_error(emb)
         if not self.encoder.output_hidden_states:
             outs = outs[-1:]
@@ -1318,14 +1337,14 @@ class PreTrainOscar(BertPreTrainedModel):
 
     def _head_outputs_f32(self, seq, pooled):
         """The three heads in fp32 (encoder.py:377-391): seq fp32 [M, H], pooled fp32 [B, H]."""
-        p = self.mlmhead.predictions
-        t = ops.linear_f32(seq, _f32(p.transform.dense.weight), _f32(p.transform.dense.bias), act=ACT_GELU)
+        p, pr = self.mlmhead.predictions, _products(self)
+        t = ops.linear_f32(seq, _f32(p.transform.dense.weight), _f32(p.transform.dense.bias), act=ACT_GELU, products=pr)
         t = ops.layernorm_rows(t, _f32(p.transform.LayerNorm.weight), _f32(p.transform.LayerNorm.bias),
                                p.transform.LayerNorm.variance_epsilon)
-        scores = ops.linear_f32(t, _f32(p.decoder.weight), _f32(p.bias))
+        scores = ops.linear_f32(t, _f32(p.decoder.weight), _f32(p.bias), products=pr)
         lin = self.token_head[0]
-        token_prob = ops.softmax_rows_f32(ops.linear_f32(seq, _f32(lin.weight), _f32(lin.bias)))
-        act = ops.linear_f32(pooled, _f32(self.next_action.linear.weight), _f32(self.next_action.linear.bias))
+        token_prob = ops.softmax_rows_f32(ops.linear_f32(seq, _f32(lin.weight), _f32(lin.bias), products=pr))
+        act = ops.linear_f32(pooled, _f32(self.next_action.linear.weight), _f32(self.next_action.linear.bias), products=pr)
         return scores, token_prob, torch.log_softmax(act, dim=-1)
 
     def forward(self, input_ids, token_type_ids=None, attention_mask=None, labels=None, token_labels=None,
@@ -1342,7 +1361,8 @@ class PreTrainOscar(BertPreTrainedModel):
         batch = {k: v for k, v in batch.items() if v is not None}
         wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         if wants_grad and _is_fp32(self):
-            raise NotImplementedError('precision "fp32" serves inference (torch.no_grad()); training runs on the bf16 kernels')
+            raise NotImplementedError('precision "fp32" / "bf16x3" serve inference (torch.no_grad()); training runs on the bf16 '
+                                      'kernels')
         if wants_grad and self.training:
             # training: HIP forward + backward, bridged to autograd so that `loss.backward()` and any torch
             # optimizer / DistributedDataParallel wrapper work as in the reference's loop

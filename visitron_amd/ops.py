@@ -1575,10 +1575,22 @@ def _f32ok(*ts):
         assert t is None or (t.dtype == torch.float32 and t.stride(-1) == 1), "fp32 path: contiguous-row fp32 tensors"
 
 
+PRODUCTS = ("fp32", "bf16x3")
+
+
+def _products_ok(products):
+    if products not in PRODUCTS:
+        raise ValueError("products must be one of %s, got %r" % (PRODUCTS, products))
+    return products == "bf16x3"
+
+
 def linear_f32(a, w, bias=None, residual=None, act=ACT_NONE, out=None, w_is_kn=False, alpha=1.0, grp_rows=0, grp_stride=0,
-               M=None, lda=None, ldc=None):
-    """out = act(alpha * a @ w.T + bias) (+ residual) in fp32 on the fp32 matrix cores.  a [M,K] (row stride lda),
-    w [N,K] (nn.Linear.weight) or [K,N] with w_is_kn."""
+               M=None, lda=None, ldc=None, products="fp32"):
+    """out = act(alpha * a @ w.T + bias) (+ residual), fp32 operands and output.  a [M,K] (row stride lda), w [N,K]
+    (nn.Linear.weight) or [K,N] with w_is_kn.  products: "fp32" -- the product on the fp32 matrix cores -- or "bf16x3" --
+    each operand split in the kernel into two bf16 terms, the product as three bf16 MFMAs with fp32 accumulation
+    (csrc/bf16x3_path.hip: |error| <= 3 * 2^-16 * |alpha| * |a| @ |w|.T to first order)."""
+    x3 = _products_ok(products)
     _require_hip(a, w, bias, residual, out)
     _f32ok(a, w, bias, residual, out)
     K = a.shape[-1]
@@ -1592,35 +1604,44 @@ def linear_f32(a, w, bias=None, residual=None, act=ACT_NONE, out=None, w_is_kn=F
         out = torch.empty((M, N), dtype=torch.float32, device=a.device)
     if ldc is None:
         ldc = out.stride(0)
-    with _timed("gemm_f32", 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N)):
-        rc = _lib.load().vt_linear_f32(_ptr(a), lda, _ptr(w), w.stride(0), 1 if w_is_kn else 0, _ptr(bias), _ptr(residual),
-                                       0 if residual is None else residual.stride(0), _ptr(out), ldc, M, N, K, int(act),
-                                       float(alpha), grp_rows, grp_stride, _stream())
-    _lib.check(rc, "vt_linear_f32")
+    lib = _lib.load()
+    name = "vt_linear_bf16x3" if x3 else "vt_linear_f32"
+    with _timed("gemm_bf16x3" if x3 else "gemm_f32", 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N)):
+        rc = getattr(lib, name)(_ptr(a), lda, _ptr(w), w.stride(0), 1 if w_is_kn else 0, _ptr(bias), _ptr(residual),
+                                0 if residual is None else residual.stride(0), _ptr(out), ldc, M, N, K, int(act),
+                                float(alpha), grp_rows, grp_stride, _stream())
+    _lib.check(rc, name)
     return out
 
 
-def attention_f32(qkv, B, S, nh, mask=None, mask_additive=False, head_scale=None, want_probs=False):
+def attention_f32(qkv, B, S, nh, mask=None, mask_additive=False, head_scale=None, want_probs=False, products="fp32"):
     """oscar/modeling_bert.py:47-72 in fp32 on the packed projection qkv fp32 [B*S, 3*nh*64]: scores = q k^T (one batched
     product), / sqrt(64) + mask, softmax, * head_mask (one row kernel, in place), context = probs v (one batched product).
+    products: the arithmetic of the two products, as in linear_f32; the softmax is the same call either way.
     -> (ctx fp32 [B*S, nh*64], probs fp32 [B, nh, S, S] or None)."""
     _require_hip(qkv, mask, head_scale)
     _f32ok(qkv, mask, head_scale)
+    x3 = _products_ok(products)
     H = nh * 64
     ld = qkv.stride(0)
     lib = _lib.load()
+    name = "vt_bmm_bf16x3" if x3 else "vt_bmm_f32"
+    bmm, tag = getattr(lib, name), ("bmm_bf16x3" if x3 else "bmm_f32")
+    flops, nbytes = 2.0 * B * nh * S * S * 64, 4.0 * B * nh * (2 * S * 64 + S * S)
     probs = torch.empty((B, nh, S, S), dtype=torch.float32, device=qkv.device)
     q, k, v = qkv, qkv[:, H:], qkv[:, 2 * H:]
-    rc = lib.vt_bmm_f32(_ptr(q), ld, S * ld, 64, _ptr(k), ld, S * ld, 64, 0, _ptr(probs), S, nh * S * S, S * S, S, S, 64, 1.0,
-                        B, nh, _stream())
-    _lib.check(rc, "vt_bmm_f32 (q k^T)")
+    with _timed(tag, flops, nbytes):
+        rc = bmm(_ptr(q), ld, S * ld, 64, _ptr(k), ld, S * ld, 64, 0, _ptr(probs), S, nh * S * S, S * S, S, S, 64, 1.0,
+                 B, nh, _stream())
+    _lib.check(rc, name + " (q k^T)")
     mode = -1 if mask is None else _mask_mode(mask, mask_additive, B, S)
     rc = lib.vt_softmax_rows_f32(_ptr(probs), S, B * nh * S, S, 0.125, _ptr(mask), mode, _ptr(head_scale), nh, S, _stream())
     _lib.check(rc, "vt_softmax_rows_f32")
     ctx = torch.empty((B * S, H), dtype=torch.float32, device=qkv.device)
-    rc = lib.vt_bmm_f32(_ptr(probs), S, nh * S * S, S * S, _ptr(v), ld, S * ld, 64, 1, _ptr(ctx), H, S * H, 64, S, 64, S, 1.0,
-                        B, nh, _stream())
-    _lib.check(rc, "vt_bmm_f32 (probs v)")
+    with _timed(tag, flops, nbytes):
+        rc = bmm(_ptr(probs), S, nh * S * S, S * S, _ptr(v), ld, S * ld, 64, 1, _ptr(ctx), H, S * H, 64, S, 64, S, 1.0,
+                 B, nh, _stream())
+    _lib.check(rc, name + " (probs v)")
     return ctx, (probs if want_probs else None)
 
 

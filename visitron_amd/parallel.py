@@ -118,7 +118,7 @@ class DataParallel(nn.Module):
         for (_, pm), (_, pr) in zip(self.module.named_parameters(), r.named_parameters()):
             pr.requires_grad_(pm.requires_grad)
         if _is_fp32(self.module):
-            set_precision(r, "fp32")
+            set_precision(r, self.module._vt_precision)
         # the routing switches a caller may have set on the master's encoder(s) are not part of the state dict
         for mm, mr in zip(self.module.modules(), r.modules()):
             for attr in ("deferred_ln", "deferred_ln_min_rows", "precise_final"):
