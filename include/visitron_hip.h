@@ -55,7 +55,9 @@ void vt_debug_set_wgrad_kernel(int mode);
 /* Autotuner result: on the calling thread's CURRENT DEVICE use kernel `variant` for linear layers of exactly this
  * shape and epilogue (filled by the host before the shape is used; one table per device, mutex-guarded).
  * kind = act | 16 (a residual / factor operand R) | 32 (the second output C2) | 64 (fp32 output) | ln_mode << 8
- * (vt_linear_ln_bf16): the out-proj with its residual and a plain dgrad of the same (M, N, K) are different entries. */
+ * (vt_linear_ln_bf16): the out-proj with its residual and a plain dgrad of the same (M, N, K) are different entries.
+ * VT_TUNE_KIND derives it from a call's arguments as the library does (VT_ACT_MUL's factor operand counts as a residual). */
+#define VT_TUNE_KIND(act, has_r, has_c2, out_f32, ln_mode) ((act) | (((has_r) || (act) == VT_ACT_MUL) ? 16 : 0) | ((has_c2) ? 32 : 0) | ((out_f32) ? 64 : 0) | ((ln_mode) << 8))
 void vt_gemm_tune(int M, int N, int K, int kind, int variant);
 /* The persistent GEMM kernels launch one workgroup per compute unit; with k > 0 they leave k compute units free (for the
  * collective kernels of a data-parallel step that run beside the backward).  Process-global, 0 by default. */
@@ -163,6 +165,11 @@ int vt_linear_lnres_bf16(const void* A, int64_t lda, const void* W, int64_t ldw,
  * mask instead of storing it.  p = 0 disables it.  Sites: 8*layer + {0 attention probabilities,
  * 1 attention.output, 2 output}; 0xE0 embeddings; 0xE1 image embedding.  In vt_linear_bf16_ex the
  * dropout is applied to act(acc + bias) BEFORE the residual add, element index m * N + n. */
+#define VT_SITE_ATTN(l) (8u * (l) + 0u)
+#define VT_SITE_SELFOUT(l) (8u * (l) + 1u)
+#define VT_SITE_OUT(l) (8u * (l) + 2u)
+#define VT_SITE_EMB 0xE0u
+#define VT_SITE_IMG 0xE1u
 int vt_apply_dropout_bf16(void* x, int64_t ld, int64_t rows, int cols, float drop_p, uint64_t drop_seed,
                           uint32_t drop_site, vt_stream_t stream);
 /* Test hook: out[i] = 1 if element i of the site is kept (head_index = b*nh + h for attention sites where

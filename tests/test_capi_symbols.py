@@ -130,3 +130,37 @@ def test_binding_refuses_what_it_has_no_rule_for(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_HEADER", missing)
     with pytest.raises(ImportError, match=re.escape(missing)):
         _lib._parse_header()
+
+
+def test_header_constants_are_the_literals_the_modules_carried():
+    from visitron_amd import _lib, ops, optim
+
+    assert _lib.CONSTANTS == {
+        "VT_OK": 0, "VT_ERR_BAD_SHAPE": -1, "VT_ERR_BAD_ALIGN": -2, "VT_ERR_NULL": -3, "VT_ERR_UNSUPPORTED": -4, "VT_ERR_HIP": -5,
+        "VT_ACT_NONE": 0, "VT_ACT_GELU": 1, "VT_ACT_TANH": 2, "VT_ACT_MUL": 3,
+        "VT_OPTIM_CHUNK": 65536, "VT_OPTIM_ENTRY_WORDS": 6, "VT_OPTIM_HYPER_FLOATS": 8}
+    assert (_lib.VT_OK, _lib.VT_ERR_BAD_SHAPE, _lib.VT_ERR_BAD_ALIGN, _lib.VT_ERR_NULL, _lib.VT_ERR_UNSUPPORTED,
+            _lib.VT_ERR_HIP) == (0, -1, -2, -3, -4, -5)
+    assert (ops.ACT_NONE, ops.ACT_GELU, ops.ACT_TANH, ops.ACT_MUL) == (0, 1, 2, 3)
+    assert (optim.CHUNK, optim.ENTRY_WORDS, optim.HYPER_FLOATS) == (65536, 6, 8)
+
+
+@pytest.mark.parametrize("define", [
+    "#define VT_X",                      # no value
+    "#define VT_X 0x10",                 # not a decimal integer
+    "#define VT_X (1 << 4)",             # an expression
+    "#define VT_X(a) ((a) + 1)",         # a function-like macro that is not on the list
+    "#define VT_KEEP_WORDS_2(B) (B)",    # a listed name as a prefix only
+    "#define VT_OK 0",                   # a constant twice
+    "#define OTHER 1",
+])
+def test_binding_refuses_a_define_outside_the_rule(monkeypatch, tmp_path, define):
+    from visitron_amd import _lib
+
+    src = open(os.path.join(ROOT, "include", "visitron_hip.h")).read()
+    hdr = tmp_path / "visitron_hip.h"
+    hdr.write_text(src.replace("#define VT_OPTIM_CHUNK 65536", define + "\n#define VT_OPTIM_CHUNK 65536"))
+    assert define in hdr.read_text()
+    monkeypatch.setattr(_lib, "_HEADER", str(hdr))
+    with pytest.raises(ImportError, match=re.escape(define)):
+        _lib._parse_header()

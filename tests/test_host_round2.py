@@ -186,7 +186,8 @@ def test_data_parallel_replicas_are_refused_with_the_way_out():
 
 # ---- round 3: host logic of the deferred-LayerNorm path and the autotuner's keys ---------------------------------
 def test_tune_kind_matches_the_library_key():
-    """ops.tune_kind must produce what VT_TUNE_KIND (csrc/gemm_bf16.hip) derives from a call's arguments."""
+    """ops.tune_kind must produce what VT_TUNE_KIND (include/visitron_hip.h) derives from a call's arguments
+    (tests/test_host_switches.py evaluates the macro itself on a grid)."""
     from visitron_amd import ops
 
     assert ops.tune_kind(ops.ACT_NONE) == 0
@@ -195,8 +196,8 @@ def test_tune_kind_matches_the_library_key():
     assert ops.tune_kind(ops.ACT_MUL) == 3 + 16                       # the factor operand counts as a residual
     assert ops.tune_kind(ops.ACT_NONE, out_f32=True) == 64
     assert ops.tune_kind(ops.ACT_GELU, ln_mode=1) == 1 + 256 and ops.tune_kind(ops.ACT_NONE, ln_mode=2) == 512
-    src = open(os.path.join(ROOT, "visitron_amd", "csrc", "gemm_bf16.hip")).read()
-    assert "((act) | ((has_r) ? 16 : 0) | ((has_c2) ? 32 : 0) | ((out_f32) ? 64 : 0) | ((ln_mode) << 8))" in src
+    src = open(os.path.join(ROOT, "include", "visitron_hip.h")).read()
+    assert "((act) | (((has_r) || (act) == VT_ACT_MUL) ? 16 : 0) | ((has_c2) ? 32 : 0) | ((out_f32) ? 64 : 0) | ((ln_mode) << 8))" in src
 
 
 def test_default_variant_table_lookup(tmp_path, monkeypatch):

@@ -7,14 +7,14 @@ import ctypes
 import os
 import re
 
+from . import switches
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "lib", "libvisitron_hip.so")
-LIB_PATH = os.environ.get("VT_HIP_LIB", LIB_PATH)   # A/B builds of the kernels (tools/): same ABI, other path
+LIB_PATH = switches.text("VT_HIP_LIB")   # A/B builds of the kernels (tools/): same ABI, other path
+if LIB_PATH is None:
+    LIB_PATH = os.path.join(_HERE, "lib", "libvisitron_hip.so")
 
-# error codes of include/visitron_hip.h
-VT_OK, VT_ERR_BAD_SHAPE, VT_ERR_BAD_ALIGN, VT_ERR_NULL, VT_ERR_UNSUPPORTED, VT_ERR_HIP = 0, -1, -2, -3, -4, -5
-
-# ---- the binding is read from the header: one declaration per entry point and struct, in include/visitron_hip.h ----------
+# ---- the binding is read from the header: one declaration per entry point, struct and constant, in include/visitron_hip.h ----
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "visitron_hip.h")
 
 # C struct -> name of the ctypes.Structure mirroring it (module attributes, set below)
@@ -25,6 +25,9 @@ _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_
             "uint32_t": ctypes.c_uint32, "float": ctypes.c_float, "vt_stream_t": ctypes.c_void_p}
 _POINTEES = ("void", "float", "int", "int32_t", "int64_t", "uint8_t", "uint16_t", "uint32_t", "uint64_t")  # data: c_void_p
 _classes = {}   # C struct name -> Structure class, filled by _parse_header
+# `#define VT_NAME <integer>` / `(-<integer>)` is a constant; any other #define must be one of these: the include guard, the
+# function-like macros (Python keeps its own ops.keep_words / site_* / tune_kind) and the two unsigned site numbers beside them
+_MACROS = ("VISITRON_HIP_H", "VT_KEEP_WORDS", "VT_SITE_ATTN", "VT_SITE_SELFOUT", "VT_SITE_OUT", "VT_SITE_EMB", "VT_SITE_IMG", "VT_TUNE_KIND")
 _DECL = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\s*)?)*)(\w+(?:\s*,\s*\w+)*)")   # [const] base [*...] name[, name]
 
 
@@ -43,12 +46,19 @@ def _ctype(base, stars, what):
 
 
 def _parse_header():
-    """include/visitron_hip.h -> _classes (the seven Structure classes) and {name: (restype, argtypes)}."""
+    """include/visitron_hip.h -> _classes (the seven Structure classes), {name: (restype, argtypes)} and {VT_NAME: integer}."""
     if not os.path.exists(_HEADER):
         raise ImportError("visitron_amd: %s not found: the ctypes binding is derived from it" % _HEADER)
     src = open(_HEADER).read()
     src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
     src = re.sub(r"#ifdef __cplusplus.*?#endif", " ", src, flags=re.S)   # the extern "C" braces
+    constants = {}
+    for define in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(.*?)[ \t]*$", src, flags=re.M):
+        c = re.fullmatch(r"(VT_\w+)[ \t]+(\d+|\(-\d+\))", define)
+        if c and c.group(1) not in constants:
+            constants[c.group(1)] = int(c.group(2).strip("()"))
+        elif c or not re.match(r"(%s)\b" % "|".join(_MACROS), define):
+            raise ImportError("visitron_amd: cannot read `#define %s` in %s" % (define, _HEADER))
     src = re.sub(r"^[ \t]*#.*$", " ", src, flags=re.M)
 
     def struct(m):
@@ -86,11 +96,13 @@ def _parse_header():
                     raise ImportError("visitron_amd: cannot read `%s` in %s" % (" ".join(stmt.split()), _HEADER))
                 argtypes.append(_ctype(a.group(1), a.group(2), stmt))
         signatures[name] = (restype, argtypes)
-    return signatures
+    return signatures, constants
 
 
-# name -> (restype, argtypes) of every entry point the header declares
-SIGNATURES = _parse_header()
+# name -> (restype, argtypes) of every entry point the header declares; VT_NAME -> value of every integer constant
+SIGNATURES, CONSTANTS = _parse_header()
+VT_OK, VT_ERR_BAD_SHAPE, VT_ERR_BAD_ALIGN, VT_ERR_NULL, VT_ERR_UNSUPPORTED, VT_ERR_HIP = (
+    CONSTANTS[c] for c in ("VT_OK", "VT_ERR_BAD_SHAPE", "VT_ERR_BAD_ALIGN", "VT_ERR_NULL", "VT_ERR_UNSUPPORTED", "VT_ERR_HIP"))
 # LayerWeights, LayerActs, LayerWeightsLn, LayerWeightsT, LayerGrads, BwdWorkspace, WgradProblem
 globals().update({_STRUCTS[c]: cls for c, cls in _classes.items()})
 

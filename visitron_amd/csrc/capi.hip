@@ -1,7 +1,7 @@
 // extern "C" entry points declared in include/visitron_hip.h.  Thin: argument checks live in the
 // *_dispatch functions next to each kernel; this file adds the layer loop of the encoder stack.
 #include "dispatch.hpp"
-#include "../../include/visitron_hip.h"
+#include "switches.hpp"
 
 // the structs of the header as the ctypes binding measures them (tests/test_capi_symbols.py pins the same numbers)
 static_assert(sizeof(vt_layer_weights) == 96 && sizeof(vt_layer_acts) == 136 && sizeof(vt_layer_weights_ln) == 96 &&
@@ -37,8 +37,7 @@ int64_t vt_attention_bwd_ws_bytes(int B, int S, int nh, int64_t rows) { return v
 static int g_attn_drop_bits = 0;
 static int attn_drop_bits() {
   if (g_attn_drop_bits == 0) {
-    const char* e = getenv("VT_ATTN_DROPOUT_BITS");
-    g_attn_drop_bits = (e && atoi(e) == 8) ? 8 : 16;
+    g_attn_drop_bits = vt_switch(VT_ATTN_DROPOUT_BITS) == 8 ? 8 : 16;
   }
   return g_attn_drop_bits;
 }
@@ -736,8 +735,7 @@ static PrefetchArgs prefetch_args(const void* p0, long b0, const void* p1, long 
 static int g_prefetch_infer = -2;
 static int prefetch_infer_mode() {
   if (g_prefetch_infer == -2) {
-    const char* e = getenv("VT_PREFETCH_INFER");
-    g_prefetch_infer = e ? atoi(e) : 3;
+    g_prefetch_infer = (int)vt_switch(VT_PREFETCH_INFER);
   }
   return g_prefetch_infer;
 }
@@ -825,10 +823,8 @@ static int g_prefetch_mode = -2;
 static long g_prefetch_max_rows = 16384;
 static int prefetch_mode(long rows) {
   if (g_prefetch_mode == -2) {
-    const char* e = getenv("VT_PREFETCH_WEIGHTS");
-    g_prefetch_mode = e ? atoi(e) : 4;
-    const char* r = getenv("VT_PREFETCH_MAX_ROWS");
-    if (r) g_prefetch_max_rows = atol(r);
+    g_prefetch_mode = (int)vt_switch(VT_PREFETCH_WEIGHTS);
+    g_prefetch_max_rows = vt_switch(VT_PREFETCH_MAX_ROWS);
   }
   return rows <= g_prefetch_max_rows ? g_prefetch_mode : 0;
 }

@@ -3,6 +3,7 @@
 #include <atomic>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/visitron_hip.h"   // the C ABI: error codes, VT_ACT_*, the dropout sites (VT_SITE_*), VT_TUNE_KIND
 
 typedef uint16_t bf16_t;  // raw bfloat16 bits in memory
 
@@ -355,14 +356,6 @@ __device__ __forceinline__ void vt_prefetch_role(const PrefetchArgs& a, int wg, 
 }
 #endif
 
-// dropout sites: layer l uses 8*l + {0: attention probs, 1: attention.output dropout, 2: output dropout};
-// 0xE0 = embeddings, 0xE1 = image embedding
-#define VT_SITE_ATTN(l) (8u * (l) + 0u)
-#define VT_SITE_SELFOUT(l) (8u * (l) + 1u)
-#define VT_SITE_OUT(l) (8u * (l) + 2u)
-#define VT_SITE_EMB 0xE0u
-#define VT_SITE_IMG 0xE1u
-
 // ---- per-device host-side state ---------------------------------------------------------------------------
 // One process may drive several GPUs from several threads (torch.nn.DataParallel, pretrain.py:93-94): everything the
 // host side remembers between calls is kept PER DEVICE (the calling thread's current device) and behind atomics.
@@ -407,11 +400,3 @@ inline std::atomic<int>& vt_deterministic_word() {
   return on;
 }
 inline bool vt_deterministic() { return vt_deterministic_word().load(std::memory_order_relaxed) != 0; }
-
-// error codes of the C ABI (include/visitron_hip.h)
-#define VT_OK 0
-#define VT_ERR_BAD_SHAPE (-1)
-#define VT_ERR_BAD_ALIGN (-2)
-#define VT_ERR_NULL (-3)
-#define VT_ERR_UNSUPPORTED (-4)
-#define VT_ERR_HIP (-5)

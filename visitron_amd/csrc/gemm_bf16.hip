@@ -705,9 +705,7 @@ void vt_gemm_set_variant(int v) {
 // mutex: threads driving different GPUs of one process (torch.nn.DataParallel) tune and look up independently.
 // The key is (M, N, K, what the epilogue does): kind = act | residual << 4 | second output << 5 | fp32 output << 6 |
 // deferred-LayerNorm mode << 8 -- a plain dgrad and the out-proj with its residual are the same (M, N, K, act) and not
-// the same kernel time (VT_TUNE_KIND below is what vt_gemm_dispatch looks up; vt_gemm_tune takes the same number).
-#define VT_TUNE_KIND(act, has_r, has_c2, out_f32, ln_mode) \
-  ((act) | ((has_r) ? 16 : 0) | ((has_c2) ? 32 : 0) | ((out_f32) ? 64 : 0) | ((ln_mode) << 8))
+// the same kernel time (VT_TUNE_KIND of include/visitron_hip.h is what vt_gemm_dispatch looks up; vt_gemm_tune takes the same number).
 struct TuneEntry { int M, N, K, kind, variant; };
 struct TuneTable { TuneEntry e[512]; int n; };
 static TuneTable g_tune_dev[VT_MAX_DEVICES];

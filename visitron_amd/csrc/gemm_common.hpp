@@ -78,7 +78,7 @@ static_assert(sizeof(GemmArgs) == 304, "GemmArgs layout");
 #define V8_SK_PART_BYTES (256 * 64 * 16)       // one part's accumulators: 256 lanes x 64 registers of 16 B
 #define V8_SK_REGION_BYTES ((long)8 * V8_SK_WGS_PER_XCD * V8_SK_PART_BYTES + 4096)   // + the counters and the error word
 
-enum { ACT_NONE = 0, ACT_GELU = 1, ACT_TANH = 2, ACT_MUL = 3 };  // MUL: out = acc * R (R = saved gelu'(pre-activation))
+enum { ACT_NONE = VT_ACT_NONE, ACT_GELU = VT_ACT_GELU, ACT_TANH = VT_ACT_TANH, ACT_MUL = VT_ACT_MUL };  // MUL: out = acc * R (R = saved gelu'(pre-activation))
 
 #define GEMM_BM 128
 #define GEMM_BN 128

@@ -4,6 +4,7 @@
 #include <cstdlib>
 #include "gemm_v7_kernels.hpp"
 #include "dispatch.hpp"
+#include "switches.hpp"
 
 // Compute units the persistent grid leaves free (vt_gemm_reserve_cus): with a collective running beside the backward (one
 // process per GPU, RCCL kernels on a few CUs) a persistent workgroup mapped onto a busy CU would stall its share of the
@@ -67,7 +68,7 @@ int vt_gemm_sk_counter_ptrs(unsigned** ptrs, int max) {
 static bool v8_take_region(GemmArgs& g) {
   const int dev = vt_current_device();
   if (dev < 0 || dev >= VT_MAX_DEVICES || g_sk_ws[dev].regions <= 0) return false;
-  static const int parts_env = [] { const char* e = getenv("VT_GEMM_SK"); return e ? atoi(e) : 2; }();   // 0 / 1: the region off
+  static const int parts_env = (int)vt_switch(VT_GEMM_SK);   // 0 / 1: the region off
   char* reg = g_sk_ws[dev].base + (long)(g_sk_ctr.fetch_add(1) % (unsigned)g_sk_ws[dev].regions) * V8_SK_REGION_BYTES;
   g.sk_ws = (float*)reg;
   g.sk_sem = (int*)(reg + V8_SK_REGION_BYTES - 4096);
@@ -113,7 +114,7 @@ static int launch_v8(const GemmArgs& g, hipStream_t stream, int mtn, bool shared
   const int th = 32 * mtn;
   g8.tiles_m = (g.M + th - 1) / th;
   {   // experiment switch: VT_GEMM_REVERSE_K = k walks the tiles of launches with K >= k backwards (0 / unset: never)
-    static const int rev_k = [] { const char* e = getenv("VT_GEMM_REVERSE_K"); return e ? atoi(e) : 0; }();
+    static const int rev_k = (int)vt_switch(VT_GEMM_REVERSE_K);
     g8.reverse = (rev_k > 0 && g.K >= rev_k) ? 1 : 0;
   }
   const int grid = vt_gemm_v8_grid(g8.tiles_m * g8.tiles_n, g8.sk_parts);

@@ -11,7 +11,6 @@
 // are all multiples of 16 moves 16 bytes per lane and finishes its last n % 4 elements one per lane; any other chunk
 // (a view that starts 4 bytes into a buffer) moves one element per lane.  The branch is uniform over the workgroup.
 #include "dispatch.hpp"
-#include "../../include/visitron_hip.h"
 
 namespace {
 

@@ -10,6 +10,7 @@
 //   pack_region_inputs  [img_feats | img_location_embeddings | 0-pad] fp32 -> bf16 K-concatenated GEMM
 //                       operand, so img_embedding + location_embeds (encoder.py:277-279) is ONE GEMM.
 #include "dispatch.hpp"
+#include "switches.hpp"
 
 __global__ void prefetch_ranges(PrefetchArgs a);   // (defined at the end of this file)
 
@@ -256,11 +257,11 @@ int vt_layernorm_dispatch(const void* x, long ldx, void* y, long ldy, const floa
   // VT_LN_FWD_ROWS: rows a wave holds at once (1 or 2; 0 = the chunked kernel above).  Measured at M = 50 820, H = 768, two
   // outputs: cold operands (tools/ln_bench.py) chunked 49.0 us, 1 row 44.2, 2 rows 44.7 (1 024 / 2 048 / 4 096 workgroups
   // within 2 us of each other); inside the pretrain step on one box (tools/experiments/ln_fwd_ab.sh) 41.8-42.1 / 39.4 / 38.1.
-  static const int rows_per_wave = [] { const char* e = getenv("VT_LN_FWD_ROWS"); return e ? atoi(e) : 2; }();
+  static const int rows_per_wave = (int)vt_switch(VT_LN_FWD_ROWS);
   if (rows_per_wave > 0 && grp_rows == 0 && (H == 768 || H == 512 || H == 1024 || H == 256)) {
     const int R = rows_per_wave >= 2 ? 2 : 1;
     long nb = (((long)M + R - 1) / R + 3) / 4;
-    static const int max_blocks = [] { const char* e = getenv("VT_LN_FWD_BLOCKS"); return e ? atoi(e) : 1024; }();
+    static const int max_blocks = (int)vt_switch(VT_LN_FWD_BLOCKS);
     if (nb > max_blocks) nb = max_blocks;
     a.n_main = (int)nb;
     a.pf.n = 0;
@@ -809,7 +810,7 @@ int vt_layernorm_bwd_dispatch(const void* x, long ldx, const void* dy, long ldy,
   // VT_LN_BWD_ROWS: rows a wave holds at once (1, 2 or 4; 0 = the chunked kernel).  Measured at M = 50 820, H = 768 with the
   // masked second copy, cold operands, reduce kernel included (tools/ln_bench.py): chunked 74.9 us, 1 row 66.6 (122 registers,
   // four waves per SIMD), 2 rows 70.3 (182), 4 rows 78.3 (302); in the pretrain step 65.3 -> 51.5 us per launch.
-  static const int rows_per_wave = [] { const char* e = getenv("VT_LN_BWD_ROWS"); return e ? atoi(e) : 1; }();
+  static const int rows_per_wave = (int)vt_switch(VT_LN_BWD_ROWS);
   if (rows_per_wave > 0 && (H == 768 || H == 512 || H == 1024 || H == 256) && (((uintptr_t)gamma) & 15) == 0) {
     const int R = rows_per_wave >= 4 ? 4 : rows_per_wave >= 2 ? 2 : 1;
     nblocks = (int)((((long)M + R - 1) / R + 3) / 4);

@@ -26,7 +26,7 @@ import os
 import torch
 from torch import nn
 
-from . import _lib, ops
+from . import _lib, ops, switches
 from .config import BertConfig
 from .ops import ACT_GELU, ACT_NONE, ACT_TANH, BF16, round_up
 
@@ -335,7 +335,7 @@ def _check_index_error(emb):
     if torch.cuda.is_current_stream_capturing():
         return   # a forward being captured into a HIP graph: no host-side look at the flag (events cannot be queried there)
     _post_index_flag(err)
-    _poll_index_flags(block=os.environ.get("VT_SYNC_ERRORS") == "1")
+    _poll_index_flags(block=switches.on("VT_SYNC_ERRORS"))
 
 
 def _dense_residual_ln(mod, hidden_states, input_tensor):
@@ -640,7 +640,7 @@ def _param_key(module_or_params):
 
 # Eval forwards with fewer token rows than this take the seven-launch layer, the others the deferred-LayerNorm loop
 # (CaptionBertEncoder.serves_deferred_ln); VT_DEFERRED_LN_MIN_ROWS or the encoder's `deferred_ln_min_rows` overrides it.
-DEFERRED_LN_MIN_ROWS_DEFAULT = 2800
+DEFERRED_LN_MIN_ROWS_DEFAULT = int(switches.SWITCHES["VT_DEFERRED_LN_MIN_ROWS"]["default"])   # 2800
 
 
 class CaptionBertEncoder(nn.Module):
@@ -661,11 +661,11 @@ class CaptionBertEncoder(nn.Module):
         # in fp32 (see run()).  It takes the returned hidden states' max-abs error against the fp32 reference from 5.9e-2 to
         # 4.9e-2 on the base config (rms 1.06e-2 -> 1.02e-2: the bf16 weights of the twelve layers set that, not the last
         # roundings) and costs 6 % of a B = 64 forward (op-by-op last layer, two fp32-output GEMM epilogues): off by default.
-        self.precise_final = os.environ.get("VT_PRECISE_FINAL", "0") == "1"
+        self.precise_final = switches.on("VT_PRECISE_FINAL")
         # inference, default: the layer loop with its LayerNorms deferred (run_ln): no LayerNorm pass, fp16 residual stream.
         # VT_DEFERRED_LN=0 (or the attribute) keeps the seven-launch layer with bf16 activations between all kernels.
-        self.deferred_ln = os.environ.get("VT_DEFERRED_LN", "1") != "0"
-        self.deferred_ln_min_rows = int(os.environ.get("VT_DEFERRED_LN_MIN_ROWS", DEFERRED_LN_MIN_ROWS_DEFAULT))   # see serves_deferred_ln
+        self.deferred_ln = switches.on("VT_DEFERRED_LN")
+        self.deferred_ln_min_rows = switches.integer("VT_DEFERRED_LN_MIN_ROWS")   # see serves_deferred_ln
         self._packed_ln = None
         self._packed_ln_key = None
 

@@ -9,11 +9,12 @@ import re
 
 import torch
 
-from . import _lib
+from . import _lib, switches
 
 BF16 = torch.bfloat16
-ACT_NONE, ACT_GELU, ACT_TANH, ACT_MUL = 0, 1, 2, 3
+ACT_NONE, ACT_GELU, ACT_TANH, ACT_MUL = (_lib.CONSTANTS["VT_ACT_" + a] for a in ("NONE", "GELU", "TANH", "MUL"))
 NO_DROP = (0.0, 0, 0)      # (p, step seed, site): dropout disabled
+# dropout sites: VT_SITE_* of include/visitron_hip.h (tests/test_host_switches.py holds the two spellings to each other)
 SITE_EMB, SITE_IMG = 0xE0, 0xE1
 
 
@@ -101,11 +102,11 @@ F16 = torch.float16
 # The seven-launch layer (training, compacted-row and diagnostic forwards) keeps its residual stream at fp16 precision: the
 # pre-LayerNorm sums are written as fp16 and every LayerNorm output also as an fp16 copy that the next residual add reads
 # (include/visitron_hip.h, vt_layer_acts::ln1_h).  VT_F16_STREAM=0: every tensor bf16, as through round 3 (A/B switch).
-F16_STREAM = os.environ.get("VT_F16_STREAM", "1") != "0"
+F16_STREAM = switches.on("VT_F16_STREAM")
 # With the fp16 stream, the TRAINING layer does not write the LayerNorm outputs' fp16 copies at all: a residual add reads the
 # previous sub-layer's fp16 sum and reconstructs its LayerNorm from the row statistics the LayerNorm kernel wrote
 # (vt_layer_acts::ln_residual_mode = 1; linear(..., residual_ln=...)).  VT_LN_RESIDUAL=0: the two-output LayerNorm of round 4.
-LN_RESIDUAL = F16_STREAM and os.environ.get("VT_LN_RESIDUAL", "1") != "0"
+LN_RESIDUAL = F16_STREAM and switches.on("VT_LN_RESIDUAL")
 
 
 def linear(a, w, bias=None, residual=None, act=ACT_NONE, out=None, out_f32=False, grp_rows=0, grp_stride=0,
@@ -260,12 +261,12 @@ def _parse_variants(text):
 GEMM_VARIANTS = _parse_variants(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "gemm_variants.def")).read())
 _variants_with = lambda flag: tuple(v for v, e in GEMM_VARIANTS.items() if flag in e["flags"])
 # the stream-K variants measured negative on MI355X at every row count tried: opt-in candidates, never timed by default
-STREAMK = os.environ.get("VT_GEMM_STREAMK", "0") == "1"
+STREAMK = switches.on("VT_GEMM_STREAMK")
 GEMM_CANDIDATES = _variants_with("TUNE_CANDIDATE") + (_variants_with("TUNE_CANDIDATE_STREAMK_ONLY") if STREAMK else ())   # file order is timing order
 
 
 # -1: shape table / heuristic; -2: the same plus the tail launch of the persistent kernel's last round (VT_GEMM_TAIL_SPLIT=1)
-AUTO_VARIANT = -2 if os.environ.get("VT_GEMM_TAIL_SPLIT") == "1" else -1
+AUTO_VARIANT = -2 if switches.on("VT_GEMM_TAIL_SPLIT") else -1
 
 
 def set_gemm_variant(v):
@@ -290,8 +291,7 @@ def multi_rank_gemm_policy(environ=None):
     real RCCL collective (no multi-GPU node in five rounds; the weight-gradient side stream competes for the same k CUs), so
     nothing switches it on by inference.  (Round 4 derived k from NCCL_MAX_NCHANNELS; withdrawn: one RCCL workgroup per
     channel is an assumption, not a measurement.)  Both policies have a profiled single-rank twin: profiles/r05/bench_b36_*.json."""
-    env = os.environ if environ is None else environ
-    v = env.get("VT_GEMM_RESERVE_CUS")
+    v = switches.text("VT_GEMM_RESERVE_CUS", environ=environ)
     if v is not None and str(v).strip().lstrip("-").isdigit():
         k = max(0, int(v))
         if 0 < k <= 64:
@@ -337,7 +337,8 @@ def force_gemm_variant(v):
 
 def tune_kind(act, residual=False, pre_act=False, out_f32=False, ln_mode=0):
     """The epilogue part of the autotuner's key, as the library derives it from a call's arguments (VT_TUNE_KIND in
-    csrc/gemm_bf16.hip): act | 16 residual / factor operand | 32 second output | 64 fp32 output | ln_mode << 8."""
+    include/visitron_hip.h; tests/test_host_switches.py holds the two to each other): act | 16 residual / factor operand |
+    32 second output | 64 fp32 output | ln_mode << 8."""
     return int(act) | (16 if (residual or act == ACT_MUL) else 0) | (32 if pre_act else 0) | (64 if out_f32 else 0) | (int(ln_mode) << 8)
 
 
@@ -404,7 +405,7 @@ def autotune_linear(M, N, K, act=ACT_NONE, residual=False, pre_act=False, device
         _tuned[key] = int(saved)
         return _tuned[key]
     default = _default_variant(key)
-    if (det or os.environ.get("VT_AUTOTUNE", "1") == "0") and usable(default):
+    if (det or not switches.on("VT_AUTOTUNE")) and usable(default):
         lib.vt_gemm_tune(M, N, K, kind, int(default))
         _tuned[key] = int(default)
         _timed_keys.discard(key)
@@ -470,7 +471,7 @@ def autotune_linear(M, N, K, act=ACT_NONE, residual=False, pre_act=False, device
     best = min(med, key=med.get)
     if usable(default) and default in med and med[default] <= med[best] * (1.0 + TUNE_KEEP_DEFAULT):
         best = default
-    if os.environ.get("VT_TUNE_VERBOSE"):
+    if switches.on("VT_TUNE_VERBOSE"):
         for v in sorted(med):
             print("  tune M=%d N=%d K=%d kind=%d variant %2d: %8.1f us %6.0f TF  (rounds %s)%s" % (
                 M, N, K, kind, v, med[v] * 1e3, 2.0 * M * N * K / (med[v] * 1e-3) * 1e-12,
@@ -491,7 +492,7 @@ def _tune_file_table():
     global _tune_file
     if _tune_file is None:
         _tune_file = {}
-        path = os.environ.get("VT_TUNE_FILE")
+        path = switches.text("VT_TUNE_FILE")
         if path and os.path.exists(path):
             import json
             with open(path) as fh:
@@ -500,7 +501,7 @@ def _tune_file_table():
 
 
 def _tune_file_store(key, best):
-    path = os.environ.get("VT_TUNE_FILE")
+    path = switches.text("VT_TUNE_FILE")
     if not path:
         return
     import json
@@ -920,7 +921,7 @@ def splitk_for(M, N, K, cus=256):
     """How many K-ranges to give the 256x256 tile list of an [M, N] output so that it covers the chip about once (0: none --
     enough tiles already, or a short K)."""
     tiles = ((M + 255) // 256) * ((N + 255) // 256)
-    if tiles * 2 > cus or K < 64 * 32 or os.environ.get("VT_SPLITK", "1") == "0":
+    if tiles * 2 > cus or K < 64 * 32 or not switches.on("VT_SPLITK"):
         return 0
     return max(2, min(cus // tiles, K // (64 * 8)))
 
@@ -1113,7 +1114,7 @@ def attn_dropout_bits():
     try:
         return int(_lib.load().vt_get_attn_dropout_bits())
     except Exception:   # noqa: BLE001 -- no HIP library on this host: the product path refuses elsewhere, loudly
-        return 8 if os.environ.get("VT_ATTN_DROPOUT_BITS") == "8" else 16
+        return 8 if switches.text("VT_ATTN_DROPOUT_BITS") == "8" else 16
 
 
 def set_attn_dropout_bits(bits):
@@ -1239,7 +1240,7 @@ def ensure_gemm_workspace(device=None):
         dev = torch.device("cuda", torch.cuda.current_device())
     if dev.index in _gemm_ws:
         return _gemm_ws[dev.index] is not None
-    regions = int(os.environ.get("VT_GEMM_WS_REGIONS", "2"))
+    regions = switches.integer("VT_GEMM_WS_REGIONS")
     lib = _lib.load()
     if regions <= 0:
         _gemm_ws[dev.index] = None
@@ -1338,7 +1339,7 @@ def softdot_attention(target, context, mask=None, want_weighted=True, want_attn=
 
 # The recurrence as ONE persistent launch (csrc/lstm_persistent.hip) where the shape allows (B <= 64, hs in 128 .. 1024):
 # VT_LSTM_PERSISTENT=0 keeps the one-launch-per-position form.  Scratch (exchange buffers + sync words) per (B, hs, device).
-LSTM_PERSISTENT = os.environ.get("VT_LSTM_PERSISTENT", "1") != "0"
+LSTM_PERSISTENT = switches.on("VT_LSTM_PERSISTENT")
 _lstm_ws = {}
 _LSTM_FORCE_TIMEOUT = [False]   # test hook: treat every persistent launch as timed out (exercises the restore + fallback)
 

@@ -21,10 +21,10 @@ import torch
 from torch.optim import Optimizer
 from torch.optim.lr_scheduler import LambdaLR
 
-# the chunk table's geometry: VT_OPTIM_CHUNK, VT_OPTIM_ENTRY_WORDS, VT_OPTIM_HYPER_FLOATS of include/visitron_hip.h
-CHUNK = 65536
-ENTRY_WORDS = 6
-HYPER_FLOATS = 8
+from . import _lib
+
+# the chunk table's geometry (include/visitron_hip.h)
+CHUNK, ENTRY_WORDS, HYPER_FLOATS = (_lib.CONSTANTS["VT_OPTIM_" + c] for c in ("CHUNK", "ENTRY_WORDS", "HYPER_FLOATS"))
 
 
 # ---- host constants: formed in double, rounded once to fp32 when they are written to the hyper buffer ----------------

@@ -12,7 +12,7 @@ the dot attentions in vt_softdot_attention_f32, every dense projection in the NT
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, switches
 from .ops import ACT_NONE, ACT_TANH, BF16, round_up
 
 
@@ -186,8 +186,7 @@ class AttnDecoderLSTM(nn.Module):
         self._pk_t = _Packed()
         # inference: replay the step from a captured HIP graph (one per input geometry).  Opt-in (VT_DECODER_GRAPH=1 or the
         # attribute): the reference's rollout is bound by its simulator, and a capture holds its own copies of the inputs.
-        import os
-        self.use_graph = os.environ.get("VT_DECODER_GRAPH", "0") == "1"
+        self.use_graph = switches.on("VT_DECODER_GRAPH")
         self._graphs = {}
 
     def _weights(self):

@@ -20,11 +20,9 @@ import ctypes
 import math
 
 import torch
-import os
-
 import torch.nn.functional as F
 
-from . import _lib, ops, training_f32
+from . import _lib, ops, switches, training_f32
 from .modeling import BertImgModelwithLocationEmbeds, PreTrainOscar, _i64, invalidate_packed_weights
 from .ops import ACT_MUL, ACT_GELU, ACT_NONE, ACT_TANH, BF16, round_up
 
@@ -110,7 +108,7 @@ class FlatParams(object):
 
 # VT_ATTN_KEEP_BITS=0: the attention backward re-derives the dropout mask from the hash instead of reading the words the
 # forward wrote (same mask either way; A/B switch)
-KEEP_BITS = os.environ.get("VT_ATTN_KEEP_BITS", "1") != "0"
+KEEP_BITS = switches.on("VT_ATTN_KEEP_BITS")
 
 
 class _TrainBuffers(object):
@@ -255,7 +253,7 @@ class PretrainEngine(object):
         # AdamW reads the reduced bf16 gradients into its fp32 moments.  VT_GRAD_COMM=fp32 / grad_comm_dtype="fp32": the
         # fp32 slab itself is all-reduced.
         if grad_comm_dtype is None:
-            grad_comm_dtype = os.environ.get("VT_GRAD_COMM", "bf16")
+            grad_comm_dtype = switches.text("VT_GRAD_COMM")
         if grad_comm_dtype not in ("bf16", "fp32"):
             raise ValueError("grad_comm_dtype must be 'bf16' or 'fp32'")
         self.grad_comm_dtype = grad_comm_dtype
@@ -279,13 +277,13 @@ class PretrainEngine(object):
         # attribute).  Measured on one GPU: +1 % when the GEMMs are the one-tile-per-workgroup kernels, -1 % with the
         # persistent kernel (its workgroups queue behind the wgrad's and still do a full share each); with a second
         # process on the same GPU it lost a lot, and beside RCCL's kernels it could not be measured here.
-        self.overlap_wgrad = os.environ.get("VT_OVERLAP_WGRAD", "0") != "0"
+        self.overlap_wgrad = switches.on("VT_OVERLAP_WGRAD")
         # one rank: AdamW per parameter range on a side stream under the backward (_train_step_adamw_under_backward)
-        self.overlap_adamw = os.environ.get("VT_OVERLAP_ADAMW", "0") != "0"
+        self.overlap_adamw = switches.on("VT_OVERLAP_ADAMW")
         self._adam_stream = None
         # the training step on the real rows only (no padding rows; vt_encoder_*_seq_bf16): same losses and gradients
         # as the padded run (tests/test_gpu_train.py); VT_COMPACT_ROWS=0 or the attribute turns it off
-        self.compact_rows = os.environ.get("VT_COMPACT_ROWS", "1") != "0"
+        self.compact_rows = switches.on("VT_COMPACT_ROWS")
         self.last_rows = None
         self.last_layout = None
         self._tuned_rows = set()
@@ -293,7 +291,7 @@ class PretrainEngine(object):
         # two launches and a host synchronisation of its own.  Since the row counts and lists ride on the step's one
         # synchronisation it wins at every batch measured (round 6, profiles/r06/compaction_by_batch.txt: B = 4 ... 36 x 228
         # +0.2 ... +3.6 %, 8 x 767 +3.2 %), so the default is 0; VT_COMPACT_MIN_ROWS restores a threshold
-        self.compact_min_rows = int(os.environ.get("VT_COMPACT_MIN_ROWS", "0"))
+        self.compact_min_rows = switches.integer("VT_COMPACT_MIN_ROWS")
         self._side_stream = None
         self._fwd_serial = 0      # forwards issued: a backward must belong to the latest one (the buffers are shared)
         if precision == "fp32":
@@ -408,7 +406,7 @@ class PretrainEngine(object):
                 self._bufs.clear()
             b = _TrainBuffers(cfg.num_hidden_layers, B * S, B, S, cfg.hidden_size, cfg.intermediate_size,
                               cfg.num_attention_heads, self.flat.p.device)
-            if self.world > 1 or os.environ.get("VT_FORCE_MULTI_RANK_GEMM") == "1":
+            if self.world > 1 or switches.on("VT_FORCE_MULTI_RANK_GEMM"):
                 # collectives share the CUs with the backward: ops.multi_rank_gemm_policy decides once whether the persistent
                 # GEMM keeps running (on CUs - k workgroups: opt-in, VT_GEMM_RESERVE_CUS=k) or stands down for the
                 # one-tile-per-workgroup kernels (default); bench.py prints the choice.  VT_FORCE_MULTI_RANK_GEMM=1 applies the
@@ -499,7 +497,7 @@ class PretrainEngine(object):
         try_compact = (allow_compact and self.compact_rows and mask is not None and mask.dim() == 2 and hs is None
                        and M >= self.compact_min_rows)
         cmask = mask.contiguous() if try_compact else None
-        early = os.environ.get("VT_STEP_OVERLAP_READBACK", "1") == "0"   # A/B switch: the transposes first, as before round 6
+        early = not switches.on("VT_STEP_OVERLAP_READBACK")   # A/B switch: the transposes first, as before round 6
         if early:
             self.refresh_derived_weights()
         counts = ops.batch_row_counts_begin(lab, tl, cmask, err, B, S)   # the step's one host synchronisation ...
@@ -538,8 +536,7 @@ class PretrainEngine(object):
             # upper edge is another tile count altogether: 7 091 real rows of a B = 36 batch are 28 row tiles of 256, 8 192 are
             # 32 (QKV: 252 tiles = one round against 288 = two); 50 845 rows of the B = 256 batch are 199, 51 200 are 200 (QKV:
             # 1 791 tiles = 7.00 rounds against 1 800 = 7.03, i.e. eight).  profiles/r06/tune_bucket_ab.txt: +1.9 % / +0.6 %.
-            bucket = round_up(Mr, int(os.environ.get("VT_TUNE_BUCKET_LARGE", "256")) if Mr >= 16384
-                              else int(os.environ.get("VT_TUNE_BUCKET_SMALL", "512")))
+            bucket = round_up(Mr, switches.integer("VT_TUNE_BUCKET_LARGE" if Mr >= 16384 else "VT_TUNE_BUCKET_SMALL"))
             if (bucket, det) not in self._tuned_rows and bucket < M:
                 ops.autotune_encoder_shapes(bucket, H, I, training=True, device=dev)
                 self._tuned_rows.add((bucket, det))
