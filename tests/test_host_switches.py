@@ -161,7 +161,7 @@ def test_library_reads_its_switches_without_a_gpu():
     base = {k: v for k, v in os.environ.items() if k not in names}
     run = lambda env: subprocess.check_output([sys.executable, "-c", code], env=dict(base, **env), cwd=ROOT).decode().split()[-3:]
     assert run({}) == ["16", "4", "3"]
-    assert run({"VT_ATTN_DROPOUT_BITS": "8", "VT_PREFETCH_WEIGHTS": "2", "VT_PREFETCH_INFER": "1"}) == ["8", "2", "1"]
+    assert run({"VT_ATTN_DROPOUT_BITS": "8", "VT_PREFETCH_WEIGHTS": "0", "VT_PREFETCH_INFER": "0"}) == ["8", "0", "0"]
     assert run({"VT_ATTN_DROPOUT_BITS": " 8"}) == ["8", "4", "3"] and run({"VT_ATTN_DROPOUT_BITS": "abc"}) == ["16", "4", "3"]
 
 

@@ -1550,8 +1550,21 @@ long vt_attention_bwd_ws_bytes_impl(int B, int S, int nh, long rows) {
 // attn_delta_rows pass (the form before round 3's last change: 330-338 against 320 us per launch at B = 256); 4: the 4-wave kernel
 // 16 (default): the 16-wave kernel where it serves (one key block, no per-query bias, keep words or no dropout), else as 8
 // 17 (default): the persistent, software-pipelined 16-wave kernel where the 16-wave kernel serves; 16: the one-pair-per-workgroup form
-static int g_attn_bwd_waves = 17;
-void vt_attn_bwd_set_waves(int w) { g_attn_bwd_waves = (w == 4 || w == 10 || w == 8 || w == 16) ? w : 17; }
+static std::atomic<int> g_attn_bwd_waves{17};
+void vt_attn_bwd_set_waves(int w) { g_attn_bwd_waves.store((w == 4 || w == 10 || w == 8 || w == 16) ? w : 17, std::memory_order_relaxed); }
+
+// The kernels by what selects them, beside each the flag of its LDS attribute (set for the kernel about to be launched):
+// the 8-wave family [det][bits][delta] (plane stores of the deterministic mode, keep words, delta formed in the kernel), the
+// 4-wave pair [det], the 16-wave kernel and its persistent form [bits]
+struct AttnBwdKernel { void (*fn)(AttnBwdArgs); VtLdsAttrOnce lds; };
+static AttnBwdKernel g_attn_bwd_w4[2] = {{attention_bwd_d64}, {attention_det_bwd_4w}};
+static AttnBwdKernel g_attn_bwd_w16p[2] = {{attention_bwd_d64_w16p<false>}, {attention_bwd_d64_w16p<true>}};
+static AttnBwdKernel g_attn_bwd_w16[2] = {{attention_bwd_d64_w16<false>}, {attention_bwd_d64_w16<true>}};
+static AttnBwdKernel g_attn_bwd_w8[2][2][2] = {
+    {{{attention_bwd_d64_w8<false, false>}, {attention_bwd_d64_w8<false, true>}},
+     {{attention_bwd_d64_w8<true, false>}, {attention_bwd_d64_w8<true, true>}}},
+    {{{attention_det_bwd_w8<false, false>}, {attention_det_bwd_w8<false, true>}},
+     {{attention_det_bwd_w8<true, false>}, {attention_det_bwd_w8<true, true>}}}};
 
 int vt_attention_bwd_dispatch(const void* qkv, long ld_qkv, const void* dctx, long ld_d, const void* ctx, long ld_ctx,
                               const float* mask, int mask_additive, const float* lse, float* delta_ws, void* dqkv,
@@ -1567,15 +1580,14 @@ int vt_attention_bwd_dispatch(const void* qkv, long ld_qkv, const void* dctx, lo
   if (B <= 0 || S <= 0 || nh <= 0 || B > 65535 || nh > 65535) return VT_ERR_BAD_SHAPE;
   if ((ld_qkv % 8) || (ld_d % 8) || (ld_ctx % 8) || (ld_dqkv % 8)) return VT_ERR_BAD_ALIGN;
   if (((uintptr_t)qkv | (uintptr_t)dctx | (uintptr_t)ctx | (uintptr_t)dqkv) & 15) return VT_ERR_BAD_ALIGN;
-  static VtLdsAttrOnce attr4, attr4d;
-  if (!attr4.set((const void*)attention_bwd_d64, AB_LDS_BYTES)) return VT_ERR_HIP;
-  if (!attr4d.set((const void*)attention_det_bwd_4w, AB_LDS_BYTES)) return VT_ERR_HIP;
   if ((seq_start == nullptr) != (seq_len == nullptr)) return VT_ERR_NULL;
   if (seq_start && (mask || rows_total <= 0)) return VT_ERR_UNSUPPORTED;   // compacted rows carry no masked keys
   const long rows = seq_start ? rows_total : (long)B * S;
   const float delta_mul = (drop && drop->thresh) ? 1.0f / drop->scale : 1.0f;
-  const bool w16 = g_attn_bwd_waves >= 16 && nkb == 1 && mask_additive != 2 && (keep_bits || !(drop && drop->thresh));
-  if (g_attn_bwd_waves != 8 && g_attn_bwd_waves < 16)
+  const int waves = g_attn_bwd_waves.load(std::memory_order_relaxed);
+  const bool w16 = waves >= 16 && nkb == 1 && mask_additive != 2 && (keep_bits || !(drop && drop->thresh));
+  const bool delta = waves == 8 || waves >= 16;   // the 8-wave kernel forms delta itself
+  if (!delta)
     hipLaunchKernelGGL(attn_delta_rows, dim3((unsigned)((S + 3) / 4), B), dim3(256), 0, stream, (const bf16_t*)dctx, ld_d,
                        (const bf16_t*)ctx, ld_ctx, delta_ws, B, S, nh, seq_start, seq_len, delta_mul);
   AttnBwdArgs a;
@@ -1589,54 +1601,27 @@ int vt_attention_bwd_dispatch(const void* qkv, long ld_qkv, const void* dctx, lo
   a.ld_qkv = ld_qkv; a.ld_d = ld_d; a.ld_dqkv = ld_dqkv; a.B = B; a.S = S; a.nh = nh;
   a.seq_start = seq_start; a.seq_len = seq_len;
   a.scale = 1.0f / sqrtf((float)head_size);
-  if (drop) a.drop = *drop; else { a.drop.thresh = 0; a.drop.seed = 0; a.drop.scale = 1.0f; }
+  a.drop = drop ? *drop : vt_no_drop();
   a.keep_bits = a.drop.thresh ? keep_bits : nullptr;
   a.ctx = (const bf16_t*)ctx; a.ld_ctx = ld_ctx; a.delta_mul = delta_mul;
-  if (w16 && g_attn_bwd_waves == 17 && (long)B * nh <= 65535 && B <= AP_MAX_B) {
-    static VtLdsAttrOnce attr17, attr17b;
-    if (!attr17.set((const void*)attention_bwd_d64_w16p<false>, AP_LDS_BYTES)) return VT_ERR_HIP;
-    if (!attr17b.set((const void*)attention_bwd_d64_w16p<true>, AP_LDS_BYTES)) return VT_ERR_HIP;
+  const bool bits = a.keep_bits != nullptr;
+  AttnBwdKernel* k;
+  dim3 grid(nh, B, nkb), block(512);
+  int lds = AB_LDS_BYTES;
+  if (w16 && waves == 17 && (long)B * nh <= 65535 && B <= AP_MAX_B) {
     const int cus = vt_device_cus();
     if (cus <= 0) return VT_ERR_HIP;
     const long pairs = (long)B * nh;
-    const unsigned grid = (unsigned)(pairs < cus ? pairs : cus);
-    if (a.keep_bits) hipLaunchKernelGGL((attention_bwd_d64_w16p<true>), dim3(grid), dim3(1024), AP_LDS_BYTES, stream, a);
-    else hipLaunchKernelGGL((attention_bwd_d64_w16p<false>), dim3(grid), dim3(1024), AP_LDS_BYTES, stream, a);
+    k = &g_attn_bwd_w16p[bits]; grid = dim3((unsigned)(pairs < cus ? pairs : cus)); block = dim3(1024); lds = AP_LDS_BYTES;
   } else if (w16) {
-    static VtLdsAttrOnce attr16, attr16b;
-    if (!attr16.set((const void*)attention_bwd_d64_w16<false>, AW_LDS_BYTES)) return VT_ERR_HIP;
-    if (!attr16b.set((const void*)attention_bwd_d64_w16<true>, AW_LDS_BYTES)) return VT_ERR_HIP;
-    if (a.keep_bits) hipLaunchKernelGGL((attention_bwd_d64_w16<true>), dim3(nh, B), dim3(1024), AW_LDS_BYTES, stream, a);
-    else hipLaunchKernelGGL((attention_bwd_d64_w16<false>), dim3(nh, B), dim3(1024), AW_LDS_BYTES, stream, a);
-  } else if (g_attn_bwd_waves == 4) {
-    if (det) hipLaunchKernelGGL(attention_det_bwd_4w, dim3(nh, B, nkb), dim3(256), AB_LDS_BYTES, stream, a);
-    else hipLaunchKernelGGL(attention_bwd_d64, dim3(nh, B, nkb), dim3(256), AB_LDS_BYTES, stream, a);
+    k = &g_attn_bwd_w16[bits]; grid = dim3(nh, B); block = dim3(1024); lds = AW_LDS_BYTES;
+  } else if (waves == 4) {
+    k = &g_attn_bwd_w4[det]; block = dim3(256);
   } else {
-    static VtLdsAttrOnce attr8, attr8b, attr8d, attr8bd;
-    if (!attr8.set((const void*)attention_bwd_d64_w8<false, false>, AB_LDS_BYTES)) return VT_ERR_HIP;
-    if (!attr8b.set((const void*)attention_bwd_d64_w8<true, false>, AB_LDS_BYTES)) return VT_ERR_HIP;
-    if (!attr8d.set((const void*)attention_bwd_d64_w8<false, true>, AB_LDS_BYTES)) return VT_ERR_HIP;
-    if (!attr8bd.set((const void*)attention_bwd_d64_w8<true, true>, AB_LDS_BYTES)) return VT_ERR_HIP;
-    const dim3 grid(nh, B, nkb);
-    if (det) {   // the same four forms with the plane stores
-      static VtLdsAttrOnce attr8x[4];
-      const void* kd[4] = {(const void*)attention_det_bwd_w8<false, false>, (const void*)attention_det_bwd_w8<true, false>,
-                           (const void*)attention_det_bwd_w8<false, true>, (const void*)attention_det_bwd_w8<true, true>};
-      for (int i = 0; i < 4; ++i)
-        if (!attr8x[i].set(kd[i], AB_LDS_BYTES)) return VT_ERR_HIP;
-      const bool delta = g_attn_bwd_waves == 8 || g_attn_bwd_waves >= 16;
-      if (delta && a.keep_bits) hipLaunchKernelGGL((attention_det_bwd_w8<true, true>), grid, dim3(512), AB_LDS_BYTES, stream, a);
-      else if (delta) hipLaunchKernelGGL((attention_det_bwd_w8<false, true>), grid, dim3(512), AB_LDS_BYTES, stream, a);
-      else if (a.keep_bits) hipLaunchKernelGGL((attention_det_bwd_w8<true, false>), grid, dim3(512), AB_LDS_BYTES, stream, a);
-      else hipLaunchKernelGGL((attention_det_bwd_w8<false, false>), grid, dim3(512), AB_LDS_BYTES, stream, a);
-    } else if (g_attn_bwd_waves == 8 || g_attn_bwd_waves >= 16) {
-      if (a.keep_bits) hipLaunchKernelGGL((attention_bwd_d64_w8<true, true>), grid, dim3(512), AB_LDS_BYTES, stream, a);
-      else hipLaunchKernelGGL((attention_bwd_d64_w8<false, true>), grid, dim3(512), AB_LDS_BYTES, stream, a);
-    } else {
-      if (a.keep_bits) hipLaunchKernelGGL((attention_bwd_d64_w8<true, false>), grid, dim3(512), AB_LDS_BYTES, stream, a);
-      else hipLaunchKernelGGL((attention_bwd_d64_w8<false, false>), grid, dim3(512), AB_LDS_BYTES, stream, a);
-    }
+    k = &g_attn_bwd_w8[det][bits][delta];
   }
+  if (!k->lds.set((const void*)k->fn, lds)) return VT_ERR_HIP;
+  hipLaunchKernelGGL(k->fn, grid, block, lds, stream, a);
   if (nkb > 1) {
     const long n = rows * (nh * 8);
     if (det) hipLaunchKernelGGL(attn_dq_round_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, dq32_ws, a.dq_plane,

@@ -328,6 +328,15 @@ __global__ __launch_bounds__(512, 4) void attention_fwd_d64(AttnArgs a) {
   ((u32x4*)(op + 32))[1] = w3;
 }
 
+// the eight instantiations, [wide][mask3][keep]: 16-bit dropout fields (exact-p mode, common.hpp), a per-query bias [B, S, S],
+// keep words written for the backward; beside each the flag of its LDS attribute
+struct AttnFwdKernel { void (*fn)(AttnArgs); VtLdsAttrOnce lds; };
+static AttnFwdKernel g_attn_fwd[2][2][2] = {
+    {{{attention_fwd_d64<false, false, false>}, {attention_fwd_d64<true, false, false>}},
+     {{attention_fwd_d64<false, true, false>}, {attention_fwd_d64<true, true, false>}}},
+    {{{attention_fwd_d64<false, false, true>}, {attention_fwd_d64<true, false, true>}},
+     {{attention_fwd_d64<false, true, true>}, {attention_fwd_d64<true, true, true>}}}};
+
 int vt_attention_fwd_dispatch(const void* qkv, long ld_qkv, const float* mask, int mask_additive, const float* head_scale, void* ctx,
                               long ld_ctx, float* lse, int B, int S, int nh, int head_size, hipStream_t stream,
                               const DropCfg* drop, const int* seq_start, const int* seq_len, uint32_t* keep_bits,
@@ -337,20 +346,11 @@ int vt_attention_fwd_dispatch(const void* qkv, long ld_qkv, const float* mask, i
   if (B <= 0 || S <= 0 || nh <= 0 || B > 65535 || nh > 65535) return VT_ERR_BAD_SHAPE;
   if ((ld_qkv % 8) || (ld_ctx % 8) || ld_qkv < 3L * nh * 64 || ld_ctx < (long)nh * 64) return VT_ERR_BAD_ALIGN;
   if (((uintptr_t)qkv | (uintptr_t)ctx) & 15) return VT_ERR_BAD_ALIGN;
-  static VtLdsAttrOnce attr, attr_keep, attr_m3, attr_keep_m3, attr_w, attr_keep_w, attr_m3_w, attr_keep_m3_w;
-  if (!attr.set((const void*)attention_fwd_d64<false, false>, ATT_LDS_BYTES)) return VT_ERR_HIP;
-  if (!attr_keep.set((const void*)attention_fwd_d64<true, false>, ATT_LDS_BYTES)) return VT_ERR_HIP;
-  if (!attr_m3.set((const void*)attention_fwd_d64<false, true>, ATT_LDS_BYTES)) return VT_ERR_HIP;
-  if (!attr_keep_m3.set((const void*)attention_fwd_d64<true, true>, ATT_LDS_BYTES)) return VT_ERR_HIP;
-  if (!attr_w.set((const void*)attention_fwd_d64<false, false, true>, ATT_LDS_BYTES)) return VT_ERR_HIP;
-  if (!attr_keep_w.set((const void*)attention_fwd_d64<true, false, true>, ATT_LDS_BYTES)) return VT_ERR_HIP;
-  if (!attr_m3_w.set((const void*)attention_fwd_d64<false, true, true>, ATT_LDS_BYTES)) return VT_ERR_HIP;
-  if (!attr_keep_m3_w.set((const void*)attention_fwd_d64<true, true, true>, ATT_LDS_BYTES)) return VT_ERR_HIP;
   AttnArgs a;
   a.qkv = (const bf16_t*)qkv; a.mask = mask; a.mask_additive = mask_additive; a.head_scale = head_scale; a.ctx = (bf16_t*)ctx; a.lse = lse;
   a.ld_qkv = ld_qkv; a.ld_ctx = ld_ctx; a.B = B; a.S = S; a.nh = nh;
   a.scale = 1.0f / sqrtf((float)head_size);
-  if (drop) a.drop = *drop; else { a.drop.thresh = 0; a.drop.seed = 0; a.drop.scale = 1.0f; }
+  a.drop = drop ? *drop : vt_no_drop();
   if ((seq_start == nullptr) != (seq_len == nullptr)) return VT_ERR_NULL;
   if (seq_start && mask) return VT_ERR_UNSUPPORTED;   // compacted rows carry no masked keys
   a.seq_start = seq_start; a.seq_len = seq_len;
@@ -369,16 +369,9 @@ int vt_attention_fwd_dispatch(const void* qkv, long ld_qkv, const float* mask, i
   }
   const bool keep = keep_bits && a.drop.thresh, m3 = mask && mask_additive == 2;
   const bool wide = vt_attn_wide(a.drop);   // exact-p mode (common.hpp): 16-bit fields
-#define ATT_FWD_LAUNCH(K_, M_)                                                                                        \
-  do {                                                                                                                \
-    if (wide) hipLaunchKernelGGL((attention_fwd_d64<K_, M_, true>), grid, dim3(512), ATT_LDS_BYTES, stream, a);       \
-    else hipLaunchKernelGGL((attention_fwd_d64<K_, M_, false>), grid, dim3(512), ATT_LDS_BYTES, stream, a);           \
-  } while (0)
-  if (keep && m3) ATT_FWD_LAUNCH(true, true);
-  else if (keep) ATT_FWD_LAUNCH(true, false);
-  else if (m3) ATT_FWD_LAUNCH(false, true);
-  else ATT_FWD_LAUNCH(false, false);
-#undef ATT_FWD_LAUNCH
+  AttnFwdKernel& k = g_attn_fwd[wide][m3][keep];
+  if (!k.lds.set((const void*)k.fn, ATT_LDS_BYTES)) return VT_ERR_HIP;
+  hipLaunchKernelGGL(k.fn, grid, dim3(512), ATT_LDS_BYTES, stream, a);
   return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
 }
 
@@ -429,7 +422,7 @@ int vt_attention_probs_dispatch(const void* qkv, long ld_qkv, const float* mask,
   a.lse = const_cast<float*>(lse);
   a.ld_qkv = ld_qkv; a.ld_ctx = 0; a.B = B; a.S = S; a.nh = nh; a.seq_start = nullptr; a.seq_len = nullptr; a.keep_bits = nullptr;
   a.scale = 1.0f / sqrtf((float)head_size);
-  a.drop.thresh = 0; a.drop.seed = 0; a.drop.scale = 1.0f;
+  a.drop = vt_no_drop();
   hipLaunchKernelGGL(attention_probs_d64, dim3(S, nh, B), dim3(256), 0, stream, a, probs);
   return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
 }

@@ -1,7 +1,6 @@
-// extern "C" entry points declared in include/visitron_hip.h.  Thin: argument checks live in the
-// *_dispatch functions next to each kernel; this file adds the layer loop of the encoder stack.
+// The C-ABI entry points declared in include/visitron_hip.h, and nothing else.  Thin: argument checks, loops and whatever
+// the host side remembers between calls live in the *_dispatch functions next to each kernel.
 #include "dispatch.hpp"
-#include "switches.hpp"
 
 // the structs of the header as the ctypes binding measures them (tests/test_capi_symbols.py pins the same numbers)
 static_assert(sizeof(vt_layer_weights) == 96 && sizeof(vt_layer_acts) == 136 && sizeof(vt_layer_weights_ln) == 96 &&
@@ -29,25 +28,14 @@ void vt_set_deterministic(int on) { vt_deterministic_word().store(on ? 1 : 0, st
 int vt_get_deterministic(void) { return vt_deterministic() ? 1 : 0; }
 int64_t vt_attention_bwd_ws_bytes(int B, int S, int nh, int64_t rows) { return vt_attention_bwd_ws_bytes_impl(B, S, nh, (long)rows); }
 
-// attention-probability dropout: 16-bit fields (default since ABI 12: p in steps of 1/65536, two keys per hash word -- the
-// reference's nn.Dropout(0.1) runs as 0.100006) or 8-bit fields (rounds 4-5's form: steps of 1/256, four keys per hash word,
-// 0.1 runs as 0.1016; the attention forward is ~5 % faster, the B = 256 step 0.15 %; common.hpp).  Process-wide; read when a
-// call builds its DropCfg, so forward and backward of one step must run under the same setting (set it before building the
-// engine; VT_ATTN_DROPOUT_BITS=8 in the environment selects the old form from the start).
-static int g_attn_drop_bits = 0;
-static int attn_drop_bits() {
-  if (g_attn_drop_bits == 0) {
-    g_attn_drop_bits = vt_switch(VT_ATTN_DROPOUT_BITS) == 8 ? 8 : 16;
-  }
-  return g_attn_drop_bits;
-}
+// attention-probability dropout in 16-bit (default) or 8-bit fields: one word for the run (vt_attn_drop_bits_word, common.hpp)
 int vt_set_attn_dropout_bits(int bits) {
   if (bits != 8 && bits != 16) return VT_ERR_UNSUPPORTED;
-  g_attn_drop_bits = bits;
+  vt_attn_drop_bits_word().store(bits, std::memory_order_relaxed);
   return VT_OK;
 }
-int vt_get_attn_dropout_bits(void) { return attn_drop_bits(); }
-float vt_attn_dropout_effective(float p) { return vt_attn_drop_ok(p, attn_drop_bits()) ? vt_attn_drop_p(p, attn_drop_bits()) : -1.0f; }
+int vt_get_attn_dropout_bits(void) { return vt_attn_drop_bits(); }
+float vt_attn_dropout_effective(float p) { return vt_attn_drop_ok(p, vt_attn_drop_bits()) ? vt_attn_drop_p(p, vt_attn_drop_bits()) : -1.0f; }
 
 int vt_batch_row_counts(const int64_t* labels, const int64_t* token_labels, const float* mask, const int32_t* err_flag, int B,
                         int S, int64_t* counts, int32_t* tile_counts, vt_stream_t stream) {
@@ -136,8 +124,8 @@ int vt_apply_dropout_bf16(void* x, int64_t ld, int64_t rows, int cols, float dro
 int vt_debug_dropout_mask(uint8_t* out, int64_t n, float drop_p, uint64_t drop_seed, uint32_t drop_site, int head_index,
                           vt_stream_t stream) {
   if (head_index >= 0) {   // attention sites: one stream per (b, h), a hash word per four keys, 8-bit thresholds (common.hpp)
-    if (!vt_attn_drop_ok(drop_p, attn_drop_bits())) return VT_ERR_UNSUPPORTED;
-    DropCfg d = vt_make_drop_attn(drop_p, drop_seed, drop_site, attn_drop_bits());
+    if (!vt_attn_drop_ok(drop_p, vt_attn_drop_bits())) return VT_ERR_UNSUPPORTED;
+    DropCfg d = vt_make_drop_attn(drop_p, drop_seed, drop_site, vt_attn_drop_bits());
     d.seed = vt_hash32(d.seed, (uint32_t)head_index);
     return vt_dropout_mask_dispatch(out, n, d, (hipStream_t)stream, 1);
   }
@@ -149,8 +137,8 @@ int vt_attention_bwd_bf16(const void* qkv, int64_t ld_qkv, const void* dctx, int
                           void* dqkv, int64_t ld_dqkv, float* dq32_ws, int B, int S, int nh, int head_size,
                           float drop_p, uint64_t drop_seed, uint32_t drop_site, const uint32_t* keep_bits,
                           vt_stream_t stream) {
-  if (!vt_attn_drop_ok(drop_p, attn_drop_bits())) return VT_ERR_UNSUPPORTED;
-  const DropCfg d = vt_make_drop_attn(drop_p, drop_seed, drop_site, attn_drop_bits());
+  if (!vt_attn_drop_ok(drop_p, vt_attn_drop_bits())) return VT_ERR_UNSUPPORTED;
+  const DropCfg d = vt_make_drop_attn(drop_p, drop_seed, drop_site, vt_attn_drop_bits());
   return vt_attention_bwd_dispatch(qkv, ld_qkv, dctx, ld_d, ctx, ld_ctx, mask, mask_additive, lse, delta_ws, dqkv,
                                    ld_dqkv, dq32_ws, B, S, nh, head_size, (hipStream_t)stream, &d, nullptr, nullptr, 0,
                                    keep_bits);
@@ -162,8 +150,8 @@ int vt_attention_bwd_seq_bf16(const void* qkv, int64_t ld_qkv, const void* dctx,
                               uint32_t drop_site, const int32_t* seq_start, const int32_t* seq_len, int64_t rows,
                               const uint32_t* keep_bits, vt_stream_t stream) {
   if (!seq_start || !seq_len) return VT_ERR_NULL;
-  if (!vt_attn_drop_ok(drop_p, attn_drop_bits())) return VT_ERR_UNSUPPORTED;
-  const DropCfg d = vt_make_drop_attn(drop_p, drop_seed, drop_site, attn_drop_bits());
+  if (!vt_attn_drop_ok(drop_p, vt_attn_drop_bits())) return VT_ERR_UNSUPPORTED;
+  const DropCfg d = vt_make_drop_attn(drop_p, drop_seed, drop_site, vt_attn_drop_bits());
   return vt_attention_bwd_dispatch(qkv, ld_qkv, dctx, ld_d, ctx, ld_ctx, nullptr, 0, lse, delta_ws, dqkv, ld_dqkv, dq32_ws,
                                    B, S, nh, head_size, (hipStream_t)stream, &d, seq_start, seq_len, rows, keep_bits);
 }
@@ -277,42 +265,11 @@ int vt_lstm_step_f32(const float* xproj, int64_t ldx, const float* h_prev, float
                                 nullptr, stream);
 }
 
-// sv_*: optional training saves laid out like the padded sequence, [B, S_sv, .] (position t of row b at (b * S_sv + t))
-static int lstm_sequence_impl(const float* xproj, int64_t ldx_b, int64_t ldx_t, float* h2_0, float* h2_1, float* c,
-                              const void* w_hh, const int32_t* lengths, float* seq_out, int64_t lds_b, int64_t lds_t,
-                              int B, int hs, int T, int reverse, vt_stream_t stream, const int32_t* xrow_start,
-                              float* sv_gates = nullptr, float* sv_c = nullptr, void* sv_h = nullptr, int64_t S_sv = 0) {
-  if (!xproj || !h2_0 || !h2_1 || !c || !w_hh) return VT_ERR_NULL;
-  if (T <= 0) return VT_ERR_BAD_SHAPE;
-  if (xrow_start && !lengths) return VT_ERR_NULL;   // compacted rows exist only below a sequence's length
-  if (sv_gates && (!sv_c || !sv_h || S_sv < T)) return VT_ERR_BAD_SHAPE;
-  float* hb[2] = {h2_0, h2_1};
-  for (int i = 0; i < T; ++i) {
-    const int t = reverse ? T - 1 - i : i;
-    LstmStepArgs a;
-    a.xrow_start = xrow_start; a.ldx_row = ldx_t;
-    a.xproj = xrow_start ? xproj : xproj + (int64_t)t * ldx_t; a.ldx = ldx_b; a.h_prev = hb[i & 1]; a.h_out = hb[(i + 1) & 1]; a.c = c;
-    a.w_hh = (const bf16_t*)w_hh; a.lengths = lengths; a.seq_out = seq_out ? seq_out + (int64_t)t * lds_t : nullptr;
-    a.ld_seq = lds_b; a.B = B; a.hs = hs; a.t = t;
-    a.sv_gates = sv_gates ? sv_gates + (int64_t)t * 4 * hs : nullptr; a.ld_svg = S_sv * 4 * hs;
-    a.sv_c = sv_gates ? sv_c + (int64_t)t * hs : nullptr; a.ld_svc = S_sv * hs;
-    a.sv_h = sv_gates ? (bf16_t*)sv_h + (int64_t)t * hs : nullptr; a.ld_svh = S_sv * hs;
-    const int rc = vt_lstm_step_dispatch(a, (hipStream_t)stream);
-    if (rc != VT_OK) return rc;
-  }
-  if (T & 1) {
-    if (hipMemcpyAsync(h2_0, h2_1, (size_t)B * hs * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) !=
-        hipSuccess)
-      return VT_ERR_HIP;
-  }
-  return VT_OK;
-}
-
 int vt_lstm_sequence_f32(const float* xproj, int64_t ldx_b, int64_t ldx_t, float* h2_0, float* h2_1, float* c,
                          const void* w_hh, const int32_t* lengths, float* seq_out, int64_t lds_b, int64_t lds_t,
                          int B, int hs, int T, int reverse, vt_stream_t stream) {
-  return lstm_sequence_impl(xproj, ldx_b, ldx_t, h2_0, h2_1, c, w_hh, lengths, seq_out, lds_b, lds_t, B, hs, T, reverse,
-                            stream, nullptr);
+  return vt_lstm_sequence_dispatch(xproj, ldx_b, ldx_t, h2_0, h2_1, c, w_hh, lengths, seq_out, lds_b, lds_t, B, hs, T, reverse,
+                                   (hipStream_t)stream, nullptr);
 }
 
 int vt_lstm_sequence_train_f32(const float* xproj, int64_t ldx_b, int64_t ldx_t, float* h2_0, float* h2_1, float* c,
@@ -320,8 +277,8 @@ int vt_lstm_sequence_train_f32(const float* xproj, int64_t ldx_b, int64_t ldx_t,
                                int B, int hs, int T, int reverse, float* sv_gates, float* sv_c, void* sv_h, int64_t S_sv,
                                vt_stream_t stream) {
   if (!sv_gates || !sv_c || !sv_h) return VT_ERR_NULL;
-  return lstm_sequence_impl(xproj, ldx_b, ldx_t, h2_0, h2_1, c, w_hh, lengths, seq_out, lds_b, lds_t, B, hs, T, reverse,
-                            stream, nullptr, sv_gates, sv_c, sv_h, S_sv);
+  return vt_lstm_sequence_dispatch(xproj, ldx_b, ldx_t, h2_0, h2_1, c, w_hh, lengths, seq_out, lds_b, lds_t, B, hs, T, reverse,
+                                   (hipStream_t)stream, nullptr, sv_gates, sv_c, sv_h, S_sv);
 }
 
 int vt_lstm_step_bwd_f32(const void* dg_next, int64_t ld_dgn, const void* w_hh_t, const float* dh_final, const float* d_out,
@@ -336,37 +293,19 @@ int vt_lstm_step_bwd_f32(const void* dg_next, int64_t ld_dgn, const void* w_hh_t
   return vt_lstm_step_bwd_dispatch(a, (hipStream_t)stream);
 }
 
-// Back-propagation through the T steps of vt_lstm_sequence_train_f32, in the reverse of the order they ran.  d_seq_out
-// [B, ., hs] (strides ldd_b, ldd_t; may be null), dh_final / dc [B, hs] (dc: in = gradient of the final cell state, it is
-// the running value afterwards), saves and dgates [B, S_sv, .]; dgates must arrive zeroed at positions >= T.
 int vt_lstm_sequence_bwd_f32(const float* d_seq_out, int64_t ldd_b, int64_t ldd_t, const float* dh_final, float* dc,
                              const void* w_hh_t, const int32_t* lengths, const float* sv_gates, const float* sv_c,
                              void* dgates, int64_t S_sv, int B, int hs, int T, int reverse, vt_stream_t stream) {
-  if (!dc || !w_hh_t || !sv_gates || !sv_c || !dgates) return VT_ERR_NULL;
-  if (T <= 0 || S_sv < T) return VT_ERR_BAD_SHAPE;
-  bf16_t* dg = (bf16_t*)dgates;
-  for (int i = T - 1; i >= 0; --i) {
-    const int t = reverse ? T - 1 - i : i;                     // the forward's i-th step ran position t
-    const int t_next = (i == T - 1) ? -1 : (reverse ? t - 1 : t + 1);
-    LstmBwdArgs a;
-    a.dg_next = t_next < 0 ? nullptr : dg + (int64_t)t_next * 4 * hs; a.ld_dgn = S_sv * 4 * hs;
-    a.w_hh_t = (const bf16_t*)w_hh_t; a.dh_final = dh_final;
-    a.d_out = d_seq_out ? d_seq_out + (int64_t)t * ldd_t : nullptr; a.ld_dout = ldd_b; a.dc = dc;
-    a.sv_gates = sv_gates + (int64_t)t * 4 * hs; a.ld_svg = S_sv * 4 * hs; a.sv_c = sv_c + (int64_t)t * hs; a.ld_svc = S_sv * hs;
-    a.dg_out = dg + (int64_t)t * 4 * hs; a.ld_dg = S_sv * 4 * hs; a.dg_out_f32 = nullptr; a.ld_dgf = 0;
-    a.lengths = lengths; a.B = B; a.hs = hs; a.t = t; a.t_next = t_next;
-    const int rc = vt_lstm_step_bwd_dispatch(a, (hipStream_t)stream);
-    if (rc != VT_OK) return rc;
-  }
-  return VT_OK;
+  return vt_lstm_sequence_bwd_dispatch(d_seq_out, ldd_b, ldd_t, dh_final, dc, w_hh_t, lengths, sv_gates, sv_c, dgates, S_sv, B,
+                                       hs, T, reverse, (hipStream_t)stream);
 }
 
 int vt_lstm_sequence_rows_f32(const float* xproj, int64_t ldx_row, const int32_t* row_start, float* h2_0, float* h2_1,
                               float* c, const void* w_hh, const int32_t* lengths, float* seq_out, int64_t lds_b,
                               int64_t lds_t, int B, int hs, int T, int reverse, vt_stream_t stream) {
   if (!row_start) return VT_ERR_NULL;
-  return lstm_sequence_impl(xproj, 0, ldx_row, h2_0, h2_1, c, w_hh, lengths, seq_out, lds_b, lds_t, B, hs, T, reverse,
-                            stream, row_start);
+  return vt_lstm_sequence_dispatch(xproj, 0, ldx_row, h2_0, h2_1, c, w_hh, lengths, seq_out, lds_b, lds_t, B, hs, T, reverse,
+                                   (hipStream_t)stream, row_start);
 }
 
 int64_t vt_lstm_sequence_persistent_ws_bytes(int B, int hs) { return vt_lstm_persistent_ws_bytes(B, hs); }
@@ -438,8 +377,8 @@ int vt_dgelu_mul_bf16(const void* g, const void* h, void* out, int64_t n, vt_str
 int vt_attention_fwd_bf16(const void* qkv, int64_t ld_qkv, const float* mask, int mask_additive, const float* head_scale, void* ctx,
                           int64_t ld_ctx, float* lse, int B, int S, int nh, int head_size, float drop_p, uint64_t drop_seed,
                           uint32_t drop_site, uint32_t* keep_bits, vt_stream_t stream) {
-  if (!vt_attn_drop_ok(drop_p, attn_drop_bits())) return VT_ERR_UNSUPPORTED;
-  const DropCfg d = vt_make_drop_attn(drop_p, drop_seed, drop_site, attn_drop_bits());
+  if (!vt_attn_drop_ok(drop_p, vt_attn_drop_bits())) return VT_ERR_UNSUPPORTED;
+  const DropCfg d = vt_make_drop_attn(drop_p, drop_seed, drop_site, vt_attn_drop_bits());
   return vt_attention_fwd_dispatch(qkv, ld_qkv, mask, mask_additive, head_scale, ctx, ld_ctx, lse, B, S, nh, head_size,
                                    (hipStream_t)stream, &d, nullptr, nullptr, keep_bits);
 }
@@ -449,8 +388,8 @@ int vt_attention_fwd_seq_bf16(const void* qkv, int64_t ld_qkv, const float* head
                               uint32_t drop_site, const int32_t* seq_start, const int32_t* seq_len, uint32_t* keep_bits,
                               vt_stream_t stream) {
   if (!seq_start || !seq_len) return VT_ERR_NULL;
-  if (!vt_attn_drop_ok(drop_p, attn_drop_bits())) return VT_ERR_UNSUPPORTED;
-  const DropCfg d = vt_make_drop_attn(drop_p, drop_seed, drop_site, attn_drop_bits());
+  if (!vt_attn_drop_ok(drop_p, vt_attn_drop_bits())) return VT_ERR_UNSUPPORTED;
+  const DropCfg d = vt_make_drop_attn(drop_p, drop_seed, drop_site, vt_attn_drop_bits());
   return vt_attention_fwd_dispatch(qkv, ld_qkv, nullptr, 0, head_scale, ctx, ld_ctx, lse, B, S, nh, head_size,
                                    (hipStream_t)stream, &d, seq_start, seq_len, keep_bits);
 }
@@ -595,9 +534,9 @@ int vt_layernorm_drop_f32(const float* x, int64_t ldx, float* y, int64_t ldy, co
 int vt_attn_softmax_train_f32(int backward, float* probs, float* probs_dropped, int64_t ld, int B, int nh, int S, float scale,
                               const float* mask, int mask_mode, const float* head_scale, float drop_p, uint64_t drop_seed,
                               uint32_t drop_site, vt_stream_t stream) {
-  if (!vt_attn_drop_ok(drop_p, attn_drop_bits())) return VT_ERR_UNSUPPORTED;
+  if (!vt_attn_drop_ok(drop_p, vt_attn_drop_bits())) return VT_ERR_UNSUPPORTED;
   return vt_attn_softmax_f32_dispatch(backward, probs, probs_dropped, ld, B, nh, S, scale, mask, mask_mode, head_scale,
-                                      vt_make_drop_attn(drop_p, drop_seed, drop_site, attn_drop_bits()), (hipStream_t)stream);
+                                      vt_make_drop_attn(drop_p, drop_seed, drop_site, vt_attn_drop_bits()), (hipStream_t)stream);
 }
 
 int vt_dgelu_f32(const float* g, const float* pre, float* out, int64_t n, vt_stream_t stream) {
@@ -634,36 +573,8 @@ int vt_action_head_g32(const float* logits, int64_t ld, const int64_t* next_acti
                                   (hipStream_t)stream);
 }
 
-}  // extern "C"
-struct StepCounterArgs {
-  unsigned* wg;
-  unsigned* sk[8];
-  int nsk;
-  long long* out;
-};
-__global__ void step_counters(StepCounterArgs a) {
-  if (threadIdx.x != 0) return;
-  const unsigned w = a.wg ? atomicExch(a.wg, 0u) : 0u;
-  unsigned s = 0;
-  for (int i = 0; i < a.nsk; ++i) s += atomicExch(a.sk[i], 0u);
-  a.out[0] = (long long)w;
-  a.out[1] = (long long)s;
-}
-extern "C" {
-
-// The two "ran out of a bounded wait" counters of the current device (vt_wgrad_turn_timeouts, vt_gemm_shared_tile_timeouts),
-// read and cleared by a one-thread kernel on `stream` into out[0] / out[1] (device int64): a training step reads them with its
-// one host synchronisation instead of three blocking 4-byte copies (25-30 us of idle GPU each at the start of every step).
-int vt_step_counters(int64_t* out2, vt_stream_t stream) {
-  if (!out2) return VT_ERR_NULL;
-  StepCounterArgs a;
-  a.wg = vt_wgrad_timeouts_devptr();
-  a.nsk = vt_gemm_sk_counter_ptrs(a.sk, 8);
-  for (int i = a.nsk; i < 8; ++i) a.sk[i] = nullptr;
-  a.out = (long long*)out2;
-  hipLaunchKernelGGL(step_counters, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
-}
+// the two bounded-wait counters of the current device in one launch (gemm_wgrad_v8.hip)
+int vt_step_counters(int64_t* out2, vt_stream_t stream) { return vt_step_counters_dispatch((long long*)out2, (hipStream_t)stream); }
 
 int vt_wgrad_turn_timeouts(unsigned* host_count) {
   if (!host_count) return VT_ERR_NULL;
@@ -708,94 +619,14 @@ int vt_ln_stream_init(const float* x, int64_t ldx, void* x_f16, int64_t lds, voi
   return vt_ln_stream_init_dispatch(x, ldx, x_f16, lds, x_bf16, ldy, stats, np, stat_rows, M, H, ln_eps, (hipStream_t)stream);
 }
 
-// CaptionBertEncoder.forward (oscar/modeling_bert.py:140-169) in eval mode with the LayerNorms deferred: five launches per
-// layer (no LayerNorm pass; the residual stream stays fp16):
-//   qkv GEMM (LN of the incoming stream folded in) -> fused attention -> out-proj GEMM (+ LN(stream) as residual; new
-//   stream + statistics) -> FFN-up GEMM (LN folded in, GELU) -> FFN-down GEMM (+ LN(stream); new stream + statistics)
-// rows != 0: the streams hold `rows` compacted token rows, sequence b = rows seq_start[b] .. + seq_len[b], every key of a
-// sequence attended (no mask) -- the layout of vt_encoder_forward_seq_bf16.
-}  // extern "C"
-
-static int prefetch4(const void* p0, long b0, const void* p1, long b1, const void* p2, long b2, const void* p3, long b3,
-                     hipStream_t stream);
-static PrefetchArgs prefetch_args(const void* p0, long b0, const void* p1, long b1, const void* p2 = nullptr, long b2 = 0,
-                                  const void* p3 = nullptr, long b3 = 0) {
-  PrefetchArgs a;
-  a.n = 0;
-  const void* p[4] = {p0, p1, p2, p3};
-  const long b[4] = {b0, b1, b2, b3};
-  for (int i = 0; i < 4; ++i)
-    if (p[i] && b[i] > 0 && !((uintptr_t)p[i] & 15)) { a.p[a.n] = p[i]; a.bytes[a.n] = b[i]; ++a.n; }
-  for (int i = a.n; i < 4; ++i) { a.p[i] = nullptr; a.bytes[i] = 0; }
-  return a;
-}
-// The inference layer loop (buffers shared by all layers; the twelve layers' weights do not survive a forward's traffic in the
-// Infinity Cache at small batch either): VT_PREFETCH_INFER = 0 off / 1 one launch per layer / 2 two launches per layer /
-// 3 (default) riding in the attention kernel's spare workgroups: no launch, measured -6 ... -9 % at B <= 16
-static int g_prefetch_infer = -2;
-static int prefetch_infer_mode() {
-  if (g_prefetch_infer == -2) {
-    g_prefetch_infer = (int)vt_switch(VT_PREFETCH_INFER);
-  }
-  return g_prefetch_infer;
-}
-
-static int encoder_forward_ln_impl(const vt_layer_weights_ln* layers, int num_layers, void* s16_a, void* sf_a, float* stats_a,
-                                   void* s16_b, void* sf_b, float* stats_b, void* qkv, void* ctx, void* mid, const float* mask,
-                                   int mask_additive, const float* head_scale, int B, int S, int H, int nh, int I, float ln_eps,
-                                   int64_t stat_rows, hipStream_t stream, long rows, const int* seq_start, const int* seq_len) {
-  if (!layers || !s16_a || !sf_a || !stats_a || !s16_b || !sf_b || !stats_b || !qkv || !ctx || !mid) return VT_ERR_NULL;
-  if (num_layers <= 0 || B <= 0 || S <= 0 || nh <= 0 || H != nh * 64 || (H % 128) || (I % 128) || H > 1024) return VT_ERR_BAD_SHAPE;
-  if (rows && (!seq_start || !seq_len || mask || rows < 0 || rows > (long)B * S)) return VT_ERR_BAD_SHAPE;
-  const int M = rows ? (int)rows : B * S, np = H / 128;
-  if (stat_rows < M) return VT_ERR_BAD_SHAPE;
-  for (int l = 0; l < num_layers; ++l) {
-    const vt_layer_weights_ln& w = layers[l];
-    int rc;
-    const int pfi = prefetch_infer_mode();
-    const long b_qkv = 6L * H * H, b_ao = 2L * H * H, b_ffn = 2L * H * I;
-    if (pfi == 1) {
-      rc = prefetch4(w.w_ao, b_ao, w.w_in, b_ffn, w.w_out, b_ffn, l + 1 < num_layers ? layers[l + 1].w_qkv : nullptr, b_qkv, stream);
-      if (rc) return rc;
-    } else if (pfi == 2) {
-      rc = prefetch4(w.w_ao, b_ao, w.w_in, b_ffn, nullptr, 0, nullptr, 0, stream);
-      if (rc) return rc;
-    }
-    rc = vt_gemm_ln_dispatch(s16_a, H, w.w_qkv, H, w.h_qkv, w.g_qkv, stats_a, np, stat_rows, ln_eps, 1, nullptr, 0, qkv, 3L * H,
-                             nullptr, 0, nullptr, M, 3 * H, H, VT_ACT_NONE, stream);
-    if (rc) return rc;
-    const DropCfg nodrop = vt_make_drop(0.f, 0, 0);
-    const PrefetchArgs pf_att = prefetch_args(w.w_ao, b_ao, w.w_in, b_ffn, w.w_out, b_ffn,
-                                              l + 1 < num_layers ? layers[l + 1].w_qkv : nullptr, b_qkv);
-    rc = vt_attention_fwd_dispatch(qkv, 3L * H, mask, mask_additive, head_scale ? head_scale + (long)l * nh : nullptr, ctx, H,
-                                   nullptr, B, S, nh, 64, stream, &nodrop, rows ? seq_start : nullptr, rows ? seq_len : nullptr,
-                                   nullptr, pfi == 3 ? &pf_att : nullptr);
-    if (rc) return rc;
-    if (pfi == 2) {
-      rc = prefetch4(w.w_out, b_ffn, l + 1 < num_layers ? layers[l + 1].w_qkv : nullptr, b_qkv, nullptr, 0, nullptr, 0, stream);
-      if (rc) return rc;
-    }
-    rc = vt_gemm_ln_dispatch(ctx, H, w.w_ao, H, w.cb_ao, w.gamma_in, stats_a, np, stat_rows, ln_eps, 2, sf_a, H, s16_b, H, sf_b,
-                             H, stats_b, M, H, H, VT_ACT_NONE, stream);
-    if (rc) return rc;
-    rc = vt_gemm_ln_dispatch(s16_b, H, w.w_in, H, w.h_in, w.g_in, stats_b, np, stat_rows, ln_eps, 1, nullptr, 0, mid, I, nullptr, 0,
-                             nullptr, M, I, H, VT_ACT_GELU, stream);
-    if (rc) return rc;
-    rc = vt_gemm_ln_dispatch(mid, I, w.w_out, I, w.cb_out, w.ln1_g, stats_b, np, stat_rows, ln_eps, 2, sf_b, H, s16_a, H, sf_a, H,
-                             stats_a, M, H, I, VT_ACT_NONE, stream);
-    if (rc) return rc;
-  }
-  return VT_OK;
-}
-
-extern "C" {
-
+// ---- the encoder stack's layer loops (encoder_loops.hip) --------------------------------------------------------------
 int vt_encoder_forward_ln_bf16(const vt_layer_weights_ln* layers, int num_layers, void* s16_a, void* sf_a, float* stats_a,
                                void* s16_b, void* sf_b, float* stats_b, void* qkv, void* ctx, void* mid, const float* mask,
                                int mask_additive, const float* head_scale, int B, int S, int H, int nh, int I, float ln_eps,
                                int64_t stat_rows, vt_stream_t stream) {
-  return encoder_forward_ln_impl(layers, num_layers, s16_a, sf_a, stats_a, s16_b, sf_b, stats_b, qkv, ctx, mid, mask, mask_additive,
-                                 head_scale, B, S, H, nh, I, ln_eps, stat_rows, (hipStream_t)stream, 0, nullptr, nullptr);
+  return vt_encoder_forward_ln_dispatch(layers, num_layers, s16_a, sf_a, stats_a, s16_b, sf_b, stats_b, qkv, ctx, mid, mask,
+                                        mask_additive, head_scale, B, S, H, nh, I, ln_eps, stat_rows, (hipStream_t)stream, 0,
+                                        nullptr, nullptr);
 }
 
 int vt_encoder_forward_ln_seq_bf16(const vt_layer_weights_ln* layers, int num_layers, void* s16_a, void* sf_a, float* stats_a,
@@ -803,165 +634,16 @@ int vt_encoder_forward_ln_seq_bf16(const vt_layer_weights_ln* layers, int num_la
                                    const float* head_scale, int B, int S, int H, int nh, int I, float ln_eps, int64_t stat_rows,
                                    int64_t rows, const int32_t* seq_start, const int32_t* seq_len, vt_stream_t stream) {
   if (rows <= 0) return VT_ERR_BAD_SHAPE;
-  return encoder_forward_ln_impl(layers, num_layers, s16_a, sf_a, stats_a, s16_b, sf_b, stats_b, qkv, ctx, mid, nullptr, 0,
-                                 head_scale, B, S, H, nh, I, ln_eps, stat_rows, (hipStream_t)stream, (long)rows, seq_start, seq_len);
+  return vt_encoder_forward_ln_dispatch(layers, num_layers, s16_a, sf_a, stats_a, s16_b, sf_b, stats_b, qkv, ctx, mid, nullptr,
+                                        0, head_scale, B, S, H, nh, I, ln_eps, stat_rows, (hipStream_t)stream, (long)rows,
+                                        seq_start, seq_len);
 }
-
-// CaptionBertEncoder.forward (oscar/modeling_bert.py:140-169): the Python loop over layers, each
-// layer = CaptionBertLayer.forward (:112-124) as 7 launches on one stream:
-//   qkv GEMM -> fused attention -> out-proj GEMM(+bias+residual) -> LayerNorm
-//   -> FFN-up GEMM(+bias+GELU) -> FFN-down GEMM(+bias+residual) -> LayerNorm
-}  // extern "C"
-
-// rows != 0: the activations hold `rows` compacted token rows (no padding rows), sequence b = rows seq_start[b] ..
-// seq_start[b] + seq_len[b]; every key of a sequence is attended (no mask).  rows == 0: B * S rows, sequence b at b * S.
-// Weight prefetch in the training layer loops (rowops.hip, prefetch_ranges): 0 off, 1 one launch per layer, 2 one launch in
-// front of every kernel that precedes a GEMM (the weights of that GEMM), -1 automatic = mode VT_PREFETCH_MODE (default 1)
-// below VT_PREFETCH_MAX_ROWS rows (default 16 384: at B = 256 the K loops run three rounds per CU at the chip's power-limited
-// rate and hide the first touch; measured level there).
-static int g_prefetch_mode = -2;
-static long g_prefetch_max_rows = 16384;
-static int prefetch_mode(long rows) {
-  if (g_prefetch_mode == -2) {
-    g_prefetch_mode = (int)vt_switch(VT_PREFETCH_WEIGHTS);
-    g_prefetch_max_rows = vt_switch(VT_PREFETCH_MAX_ROWS);
-  }
-  return rows <= g_prefetch_max_rows ? g_prefetch_mode : 0;
-}
-static int prefetch4(const void* p0, long b0, const void* p1, long b1, const void* p2, long b2, const void* p3, long b3,
-                     hipStream_t stream) {
-  const void* p[4] = {p0, p1, p2, p3};
-  const long b[4] = {b0, b1, b2, b3};
-  return vt_prefetch_dispatch(p, b, 4, stream);
-}
-// Mode 3: the same reads on a SIDE stream of the library's own, started behind an event on the caller's stream and never
-// waited for (nothing depends on them): issued in front of the attention kernels, whose waves leave registers and memory
-// bandwidth free -- the persistent GEMMs hold every register of a CU they run on, so beside them a prefetch would only queue.
-struct PrefetchSide {
-  hipStream_t stream;
-  hipEvent_t ev[64];
-  unsigned next;
-  bool ok;
-};
-static PrefetchSide* prefetch_side() {
-  static PrefetchSide side[16];
-  static bool made[16] = {false};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-  if (!made[dev]) {
-    made[dev] = true;
-    PrefetchSide& s = side[dev];
-    s.ok = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess;
-    for (int i = 0; s.ok && i < 64; ++i) s.ok = hipEventCreateWithFlags(&s.ev[i], hipEventDisableTiming) == hipSuccess;
-    s.next = 0;
-  }
-  return side[dev].ok ? &side[dev] : nullptr;
-}
-static int prefetch4_side(const void* p0, long b0, const void* p1, long b1, const void* p2, long b2, const void* p3, long b3,
-                          hipStream_t stream) {
-  PrefetchSide* s = prefetch_side();
-  if (!s) return prefetch4(p0, b0, p1, b1, p2, b2, p3, b3, stream);
-  hipEvent_t e = s->ev[s->next++ & 63];
-  if (hipEventRecord(e, stream) != hipSuccess || hipStreamWaitEvent(s->stream, e, 0) != hipSuccess) return VT_ERR_HIP;
-  return prefetch4(p0, b0, p1, b1, p2, b2, p3, b3, s->stream);
-}
-
-static int encoder_forward_impl(const vt_layer_weights* layers, const vt_layer_acts* acts, int num_layers, const void* x,
-                                const float* mask, int mask_additive, const float* head_scale, int B, int S, int H, int nh,
-                                int I, float ln_eps, float p_hidden, float p_attn, uint64_t drop_seed, hipStream_t stream,
-                                long rows, const int* seq_start, const int* seq_len) {
-  if (!layers || !acts || !x) return VT_ERR_NULL;
-  if (num_layers <= 0 || B <= 0 || S <= 0 || nh <= 0 || H != nh * 64 || (H % 64) || (I % 64)) return VT_ERR_BAD_SHAPE;
-  if (rows && (!seq_start || !seq_len || mask || rows < 0 || rows > (long)B * S)) return VT_ERR_BAD_SHAPE;
-  const int M = rows ? (int)rows : B * S;
-  const void* cur = x;
-  const void* cur_h = nullptr;   // fp16 copy of `cur` (the previous layer's output), when that layer kept one -- or, with
-                                 // cur_ln set, the previous layer's fp16 pre-LayerNorm sum whose LayerNorm `cur` is
-  VtLnResidual cur_ln = {nullptr, nullptr, nullptr, nullptr};
-  for (int l = 0; l < num_layers; ++l) {
-    const vt_layer_weights& w = layers[l];
-    const vt_layer_acts& a = acts[l];
-    if (!a.qkv || !a.ctx || !a.attn_pre || !a.attn_out || !a.mid || !a.out_pre || !a.out) return VT_ERR_NULL;
-    int rc;
-    const int pf = prefetch_mode(M);
-    const long b_qkv = 6L * H * H, b_ao = 2L * H * H, b_ffn = 2L * H * I;   // bytes of the layer's four bf16 weight matrices
-    if (pf == 1) {   // this layer's later weights and the next layer's first one, in one launch
-      rc = prefetch4(w.w_ao, b_ao, w.w_in, b_ffn, w.w_out, b_ffn, l + 1 < num_layers ? layers[l + 1].w_qkv : nullptr, b_qkv, stream);
-      if (rc) return rc;
-    } else if (pf == 2) {
-      rc = prefetch4(w.w_ao, b_ao, nullptr, 0, nullptr, 0, nullptr, 0, stream);
-      if (rc) return rc;
-    }
-    rc = vt_gemm_dispatch(cur, H, w.w_qkv, H, w.b_qkv, nullptr, 0, a.qkv, 3L * H, M, 3 * H, H, VT_ACT_NONE, 0, 0, 0, stream);
-    if (rc) return rc;
-    if (!vt_attn_drop_ok(p_attn, attn_drop_bits())) return VT_ERR_UNSUPPORTED;
-    const DropCfg d_att = vt_make_drop_attn(p_attn, drop_seed, VT_SITE_ATTN(l), attn_drop_bits());
-    const DropCfg d_so = vt_make_drop(p_hidden, drop_seed, VT_SITE_SELFOUT(l));
-    const DropCfg d_out = vt_make_drop(p_hidden, drop_seed, VT_SITE_OUT(l));
-    if (pf == 3) {   // beside the attention kernel: the three weights the rest of this layer reads, and the next layer's first
-      rc = prefetch4_side(w.w_ao, b_ao, w.w_in, b_ffn, w.w_out, b_ffn, l + 1 < num_layers ? layers[l + 1].w_qkv : nullptr, b_qkv, stream);
-      if (rc) return rc;
-    }
-    rc = vt_attention_fwd_dispatch(a.qkv, 3L * H, mask, mask_additive, head_scale ? head_scale + (long)l * nh : nullptr, a.ctx, H,
-                                   a.lse, B, S, nh, 64, stream, &d_att, rows ? seq_start : nullptr, rows ? seq_len : nullptr,
-                                   a.keep_bits);
-    if (rc) return rc;
-    // The residual stream.  Plain form: every tensor bf16.  With the layer's fp16 copies present (ln1_h / ln2_h non-null,
-    // vt_layer_acts): the pre-LayerNorm sums attn_pre / out_pre are written and read as fp16, each LayerNorm writes its
-    // output twice -- bf16 for the next GEMM's A operand (and the backward), fp16 for the next sub-layer's residual add --
-    // so the stream itself is rounded to 11 significant bits instead of 8 (north_star's 5e-2 on the hidden states of the
-    // path training runs: 5.8e-2 with the bf16 stream on the stress weights).
-    // ln_residual_mode 1: the fp16 copies are never written -- a residual add reads the previous sub-layer's fp16 SUM and
-    // reconstructs its LayerNorm from the row statistics that LayerNorm's kernel wrote (GemmArgs::r_mean); the LayerNorm
-    // kernel then has one output instead of two.
-    const bool rln = a.ln_residual_mode == 1;
-    if (rln && (!a.ln1_mean || !a.ln1_rstd || !a.ln2_mean || !a.ln2_rstd)) return VT_ERR_NULL;
-    if (a.ln_residual_mode != 0 && !rln) return VT_ERR_UNSUPPORTED;
-    const bool h16 = rln || (a.ln1_h && a.ln2_h);
-    const void* res = cur_h ? cur_h : cur;
-    if (pf == 2) {
-      rc = prefetch4(w.w_in, b_ffn, w.w_out, b_ffn, nullptr, 0, nullptr, 0, stream);
-      if (rc) return rc;
-    }
-    rc = vt_gemm_dispatch(a.ctx, H, w.w_ao, H, w.b_ao, res, H, a.attn_pre, H, M, H, H, VT_ACT_NONE,
-                          (h16 ? 2 : 0) | (cur_h ? 4 : 0), 0, 0, stream, nullptr, 0, &d_so, cur_ln.mean ? &cur_ln : nullptr);
-    if (rc) return rc;
-    // mode 4: the LayerNorm kernels carry the prefetch in spare workgroups -- LayerNorm 1 the two FFN weights, LayerNorm 2 the
-    // next layer's attention weights (no launch of its own)
-    const PrefetchArgs pf_ln1 = prefetch_args(w.w_in, b_ffn, w.w_out, b_ffn);
-    const PrefetchArgs pf_ln2 = l + 1 < num_layers ? prefetch_args(layers[l + 1].w_qkv, b_qkv, layers[l + 1].w_ao, b_ao)
-                                                   : prefetch_args(nullptr, 0, nullptr, 0);
-    rc = vt_layernorm_dispatch(a.attn_pre, H, a.attn_out, H, w.ln1_g, w.ln1_b, a.ln1_mean, a.ln1_rstd, M, H, ln_eps, 0, 0, stream,
-                               h16 ? 1 : 0, (h16 && !rln) ? a.ln1_h : nullptr, H, pf == 4 ? &pf_ln1 : nullptr);
-    if (rc) return rc;
-    rc = vt_gemm_dispatch(a.attn_out, H, w.w_in, H, w.b_in, nullptr, 0, a.mid, I, M, I, H, VT_ACT_GELU, 0, 0, 0, stream,
-                          a.mid_pre, I);
-    if (rc) return rc;
-    const VtLnResidual ln1 = {a.ln1_mean, a.ln1_rstd, w.ln1_g, w.ln1_b};
-    if (pf == 2 && l + 1 < num_layers) {
-      rc = prefetch4(layers[l + 1].w_qkv, b_qkv, nullptr, 0, nullptr, 0, nullptr, 0, stream);
-      if (rc) return rc;
-    }
-    rc = vt_gemm_dispatch(a.mid, I, w.w_out, I, w.b_out, rln ? a.attn_pre : (h16 ? a.ln1_h : a.attn_out), H, a.out_pre, H, M, H, I,
-                          VT_ACT_NONE, h16 ? 6 : 0, 0, 0, stream, nullptr, 0, &d_out, rln ? &ln1 : nullptr);
-    if (rc) return rc;
-    rc = vt_layernorm_dispatch(a.out_pre, H, a.out, H, w.ln2_g, w.ln2_b, a.ln2_mean, a.ln2_rstd, M, H, ln_eps, 0, 0, stream,
-                               h16 ? 1 : 0, (h16 && !rln) ? a.ln2_h : nullptr, H, pf == 4 ? &pf_ln2 : nullptr);
-    if (rc) return rc;
-    cur = a.out;
-    cur_h = rln ? a.out_pre : (h16 ? a.ln2_h : nullptr);
-    cur_ln = rln ? VtLnResidual{a.ln2_mean, a.ln2_rstd, w.ln2_g, w.ln2_b} : VtLnResidual{nullptr, nullptr, nullptr, nullptr};
-  }
-  return VT_OK;
-}
-
-extern "C" {
 
 int vt_encoder_forward_bf16(const vt_layer_weights* layers, const vt_layer_acts* acts, int num_layers, const void* x,
                             const float* mask, int mask_additive, const float* head_scale, int B, int S, int H, int nh,
                             int I, float ln_eps, float p_hidden, float p_attn, uint64_t drop_seed, vt_stream_t stream) {
-  return encoder_forward_impl(layers, acts, num_layers, x, mask, mask_additive, head_scale, B, S, H, nh, I, ln_eps, p_hidden,
-                              p_attn, drop_seed, (hipStream_t)stream, 0, nullptr, nullptr);
+  return vt_encoder_forward_dispatch(layers, acts, num_layers, x, mask, mask_additive, head_scale, B, S, H, nh, I, ln_eps,
+                                     p_hidden, p_attn, drop_seed, (hipStream_t)stream, 0, nullptr, nullptr);
 }
 
 int vt_encoder_forward_seq_bf16(const vt_layer_weights* layers, const vt_layer_acts* acts, int num_layers, const void* x,
@@ -969,185 +651,23 @@ int vt_encoder_forward_seq_bf16(const vt_layer_weights* layers, const vt_layer_a
                                 float p_attn, uint64_t drop_seed, int64_t rows, const int32_t* seq_start,
                                 const int32_t* seq_len, vt_stream_t stream) {
   if (rows <= 0) return VT_ERR_BAD_SHAPE;
-  return encoder_forward_impl(layers, acts, num_layers, x, nullptr, 0, head_scale, B, S, H, nh, I, ln_eps, p_hidden, p_attn,
-                              drop_seed, (hipStream_t)stream, (long)rows, seq_start, seq_len);
+  return vt_encoder_forward_dispatch(layers, acts, num_layers, x, nullptr, 0, head_scale, B, S, H, nh, I, ln_eps, p_hidden,
+                                     p_attn, drop_seed, (hipStream_t)stream, (long)rows, seq_start, seq_len);
 }
 
-// Weight prefetch of the layer loops (see prefetch_mode / prefetch_infer_mode above): training 0 off, 1 one launch per layer,
-// 2 a launch per GEMM pair, 3 side stream, 4 (default) in the LayerNorm kernels' spare workgroups; inference 0 off, 1 / 2
-// launches, 3 (default) in the attention kernel's spare workgroups.  -1 keeps a setting.  Values are never changed by it.
-int vt_set_weight_prefetch(int training_mode, int inference_mode) {
-  if (training_mode < -1 || training_mode > 4 || inference_mode < -1 || inference_mode > 3) return VT_ERR_UNSUPPORTED;
-  (void)prefetch_mode(0);
-  (void)prefetch_infer_mode();
-  if (training_mode >= 0) g_prefetch_mode = training_mode;
-  if (inference_mode >= 0) g_prefetch_infer = inference_mode;
-  return VT_OK;
-}
-int vt_get_weight_prefetch(int inference) {
-  (void)prefetch_mode(0);
-  return inference ? prefetch_infer_mode() : g_prefetch_mode;
-}
-
-// Backward of CaptionBertEncoder (oscar/modeling_bert.py:140-169) = the reverse layer loop; per layer
-// 4 dgrad GEMMs (residual adds and the dGELU fused in their epilogues), 2 LayerNorm backwards, the
-// fused attention backward and ONE grouped weight-gradient launch for the layer's four matrices
-// (bias gradients ride along in it).
-}  // extern "C"
-
-// Events that order the weight-gradient launches on the side stream against the dgrad chain (one pair per layer of
-// a call; created once per device, never destroyed: a few dozen host-side handles).
-#define VT_BWD_MAX_LAYERS 64
-static hipEvent_t* bwd_events(int which) {
-  static hipEvent_t ev[16][2][VT_BWD_MAX_LAYERS];
-  static bool made[16] = {false};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-  if (!made[dev]) {
-    for (int k = 0; k < 2; ++k)
-      for (int i = 0; i < VT_BWD_MAX_LAYERS; ++i)
-        if (hipEventCreateWithFlags(&ev[dev][k][i], hipEventDisableTiming) != hipSuccess) return nullptr;
-    made[dev] = true;
-  }
-  return ev[dev][which];
-}
-
-// The reverse layer loop.  With a second workspace set (ws_b) and a side stream the four weight gradients of layer l
-// run on the side stream while the main stream goes on with layer l-1: the grouped wgrad launch keeps 216 of the 256
-// CUs busy (108 tiles x 2 row ranges), the next layer's LayerNorm backward and whatever else is not a persistent
-// kernel fills the rest.  Layer l works in workspace set (layer0 + l) & 1, so the buffers a wgrad still reads are
-// rewritten two layers later, behind a wait on that wgrad's completion event; before returning the main stream waits
-// for every wgrad of the call.
-static int encoder_backward_impl(const vt_layer_weights* layers, const vt_layer_weights_t* layers_t,
-                                 const vt_layer_acts* acts, const vt_layer_grads* grads, int num_layers, const void* x,
-                                 const float* mask, int mask_additive, void* g, const vt_bwd_workspace* ws_a,
-                                 const vt_bwd_workspace* ws_b, int B, int S, int H, int nh, int I, float ln_eps,
-                                 int accumulate, float p_hidden, float p_attn, uint64_t drop_seed, int layer0,
-                                 hipStream_t stream, hipStream_t side, long rows = 0, const int* seq_start = nullptr,
-                                 const int* seq_len = nullptr) {
-  if (!layers || !layers_t || !acts || !grads || !x || !g || !ws_a) return VT_ERR_NULL;
-  if (rows && (!seq_start || !seq_len || mask || rows < 0 || rows > (long)B * S)) return VT_ERR_BAD_SHAPE;
-  const bool overlap = ws_b != nullptr && side != nullptr && side != stream;
-  for (int k = 0; k < (overlap ? 2 : 1); ++k) {
-    const vt_bwd_workspace* ws = k ? ws_b : ws_a;
-    if (p_hidden > 0.f && (!ws->g_pre_d || !ws->g_pre2_d)) return VT_ERR_NULL;
-    if (!ws->g_pre || !ws->g_pre2 || !ws->g_mid || !ws->g_ctx || !ws->g_qkv || !ws->delta || !ws->ln_partial) return VT_ERR_NULL;
-  }
-  if (num_layers <= 0 || B <= 0 || S <= 0 || nh <= 0 || H != nh * 64 || (I % 64)) return VT_ERR_BAD_SHAPE;
-  if (overlap && num_layers > VT_BWD_MAX_LAYERS) return VT_ERR_BAD_SHAPE;
-  hipEvent_t* ev_in = overlap ? bwd_events(0) : nullptr;    // E[l]: layer l's wgrad operands are complete (main)
-  hipEvent_t* ev_done = overlap ? bwd_events(1) : nullptr;  // F[l]: layer l's wgrad has finished (side)
-  if (overlap && (!ev_in || !ev_done)) return VT_ERR_HIP;
-  const int M = rows ? (int)rows : B * S;
-  for (int l = num_layers - 1; l >= 0; --l) {
-    const vt_layer_weights& w = layers[l];
-    const vt_layer_weights_t& wt = layers_t[l];
-    const vt_layer_acts& a = acts[l];
-    const vt_layer_grads& d = grads[l];
-    if (!a.mid_pre || !a.lse) return VT_ERR_NULL;
-    const void* x_in = l == 0 ? x : acts[l - 1].out;
-    const vt_bwd_workspace* ws = (overlap && ((layer0 + l) & 1)) ? ws_b : ws_a;
-    // this layer rewrites the set that the wgrad of layer l + 2 reads
-    if (overlap && l + 2 < num_layers && hipStreamWaitEvent(stream, ev_done[l + 2], 0) != hipSuccess) return VT_ERR_HIP;
-    int rc;
-    // dropout sites of this layer (the forward used layer index layer0 + l)
-    if (!vt_attn_drop_ok(p_attn, attn_drop_bits())) return VT_ERR_UNSUPPORTED;
-    const DropCfg d_att = vt_make_drop_attn(p_attn, drop_seed, VT_SITE_ATTN(layer0 + l), attn_drop_bits());
-    const DropCfg d_so = vt_make_drop(p_hidden, drop_seed, VT_SITE_SELFOUT(layer0 + l));
-    const DropCfg d_out = vt_make_drop(p_hidden, drop_seed, VT_SITE_OUT(layer0 + l));
-    // with hidden dropout the gradient of a dense output is the pre-LayerNorm gradient times the mask
-    void* g_pre_dn = p_hidden > 0.f ? ws->g_pre_d : ws->g_pre;
-    void* g_pre2_dn = p_hidden > 0.f ? ws->g_pre2_d : ws->g_pre2;
-    const int pf = prefetch_mode(M);
-    const long b_qkv = 6L * H * H, b_ao = 2L * H * H, b_ffn = 2L * H * I;   // the transposed copies have the same sizes
-    if (pf == 1) {   // the four transposed weight copies this layer's dgrad GEMMs read
-      rc = prefetch4(wt.wt_out, b_ffn, wt.wt_in, b_ffn, wt.wt_ao, b_ao, wt.wt_qkv, b_qkv, stream);
-      if (rc) return rc;
-    } else if (pf == 2) {
-      rc = prefetch4(wt.wt_out, b_ffn, wt.wt_in, b_ffn, nullptr, 0, nullptr, 0, stream);
-      if (rc) return rc;
-    } else if (pf == 3 && l == num_layers - 1) {   // the call's first layer: beside its LayerNorm backward
-      rc = prefetch4_side(wt.wt_out, b_ffn, wt.wt_in, b_ffn, wt.wt_ao, b_ao, nullptr, 0, stream);
-      if (rc) return rc;
-    }
-    // LayerNorm 2 backward: dL/d(out_pre)
-    const int h16 = ((a.ln1_h && a.ln2_h) || a.ln_residual_mode == 1) ? 1 : 0;   // the forward kept the pre-LayerNorm sums as fp16 (see encoder_forward_impl)
-    const PrefetchArgs pf_ln2 = prefetch_args(wt.wt_out, b_ffn, wt.wt_in, b_ffn);   // mode 4: riding in the reduce kernels
-    const PrefetchArgs pf_ln1 = prefetch_args(wt.wt_ao, b_ao, wt.wt_qkv, b_qkv);
-    rc = vt_layernorm_bwd_dispatch(a.out_pre, H, g, H, w.ln2_g, ws->g_pre, H, d.d_ln2_g, d.d_ln2_b, ws->ln_partial, M, H,
-                                   ln_eps, accumulate, stream, p_hidden > 0.f ? ws->g_pre_d : nullptr, H, &d_out, h16,
-                                   pf == 4 ? &pf_ln2 : nullptr);
-    if (rc) return rc;
-    // through output.dense and the GELU: g_mid = (g_pre . W_out) * gelu'(pre-activation) (saved in mid_pre)
-    rc = vt_gemm_dispatch(g_pre_dn, H, wt.wt_out, H, nullptr, a.mid_pre, I, ws->g_mid, I, M, I, H, VT_ACT_MUL, 0, 0, 0, stream);
-    if (rc) return rc;
-    // through intermediate.dense, plus the residual branch: dL/d(attn_out) -> g
-    rc = vt_gemm_dispatch(ws->g_mid, I, wt.wt_in, I, nullptr, ws->g_pre, H, g, H, M, H, I, VT_ACT_NONE, 0, 0, 0, stream);
-    if (rc) return rc;
-    if (pf == 2) {
-      rc = prefetch4(wt.wt_ao, b_ao, wt.wt_qkv, b_qkv, nullptr, 0, nullptr, 0, stream);
-      if (rc) return rc;
-    }
-    // LayerNorm 1 backward: dL/d(attn_pre)
-    rc = vt_layernorm_bwd_dispatch(a.attn_pre, H, g, H, w.ln1_g, ws->g_pre2, H, d.d_ln1_g, d.d_ln1_b, ws->ln_partial, M, H,
-                                   ln_eps, accumulate, stream, p_hidden > 0.f ? ws->g_pre2_d : nullptr, H, &d_so, h16,
-                                   pf == 4 ? &pf_ln1 : nullptr);
-    if (rc) return rc;
-    // through attention.output.dense: dL/d(ctx)
-    rc = vt_gemm_dispatch(g_pre2_dn, H, wt.wt_ao, H, nullptr, nullptr, 0, ws->g_ctx, H, M, H, H, VT_ACT_NONE, 0, 0, 0, stream);
-    if (rc) return rc;
-    if (pf == 3) {   // beside the attention backward: this layer's last dgrad weight and the three of the layer below
-      const vt_layer_weights_t* nx = l > 0 ? &layers_t[l - 1] : nullptr;
-      rc = prefetch4_side(wt.wt_qkv, b_qkv, nx ? nx->wt_out : nullptr, b_ffn, nx ? nx->wt_in : nullptr, b_ffn,
-                          nx ? nx->wt_ao : nullptr, b_ao, stream);
-      if (rc) return rc;
-    }
-    rc = vt_attention_bwd_dispatch(a.qkv, 3L * H, ws->g_ctx, H, a.ctx, H, mask, mask_additive, a.lse, ws->delta, ws->g_qkv,
-                                   3L * H, ws->dq32, B, S, nh, 64, stream, &d_att, rows ? seq_start : nullptr,
-                                   rows ? seq_len : nullptr, rows, a.keep_bits);
-    if (rc) return rc;
-    // through the packed q|k|v projection, plus the residual branch: dL/d(layer input) -> g
-    rc = vt_gemm_dispatch(ws->g_qkv, 3L * H, wt.wt_qkv, 3L * H, nullptr, ws->g_pre2, H, g, H, M, H, 3 * H, VT_ACT_NONE, 0, 0, 0, stream);
-    if (rc) return rc;
-    // the four weight (+bias) gradients of this layer in one grouped launch
-    WgradArgs wa;
-    wa.nprob = 4;
-    wa.M = M;
-    auto set = [&](int i, const void* dY, long ldy, const void* X, long ldx, float* dW, float* db, int N, int K) {
-      WgradProblem& P = wa.p[i];
-      P.dY = (const bf16_t*)dY; P.ldy = ldy; P.X = (const bf16_t*)X; P.ldx = ldx; P.dW = dW; P.ldw = K; P.db = db;
-      P.N = N; P.K = K; P.accumulate = accumulate; P.tiles_k = 0; P.tile_begin = 0;
-    };
-    set(0, ws->g_mid, I, a.attn_out, H, d.d_w_in, d.d_b_in, I, H);
-    set(1, g_pre_dn, H, a.mid, I, d.d_w_out, d.d_b_out, H, I);
-    set(2, ws->g_qkv, 3L * H, x_in, H, d.d_w_qkv, d.d_b_qkv, 3 * H, H);
-    set(3, g_pre2_dn, H, a.ctx, H, d.d_w_ao, d.d_b_ao, H, H);
-    for (int i = 4; i < WG_MAX_PROBLEMS; ++i) wa.p[i] = wa.p[0];
-    if (overlap) {
-      if (hipEventRecord(ev_in[l], stream) != hipSuccess || hipStreamWaitEvent(side, ev_in[l], 0) != hipSuccess) return VT_ERR_HIP;
-      rc = vt_wgrad_dispatch(wa, side);
-      if (rc) return rc;
-      if (hipEventRecord(ev_done[l], side) != hipSuccess) return VT_ERR_HIP;
-    } else {
-      rc = vt_wgrad_dispatch(wa, stream);
-      if (rc) return rc;
-    }
-  }
-  if (overlap)   // the caller's next work on the main stream (all-reduce, optimizer) sees every weight gradient
-    for (int l = (num_layers < 2 ? num_layers : 2) - 1; l >= 0; --l)
-      if (hipStreamWaitEvent(stream, ev_done[l], 0) != hipSuccess) return VT_ERR_HIP;
-  return VT_OK;
-}
-
-extern "C" {
+// Weight prefetch of the layer loops: training 0 off, 4 (default) in the LayerNorm kernels' spare workgroups; inference 0 off,
+// 3 (default) in the attention kernel's spare workgroups.  -1 keeps a setting; any other number is refused.
+int vt_set_weight_prefetch(int training_mode, int inference_mode) { return vt_weight_prefetch_set(training_mode, inference_mode); }
+int vt_get_weight_prefetch(int inference) { return vt_weight_prefetch_get(inference); }
 
 int vt_encoder_backward_bf16(const vt_layer_weights* layers, const vt_layer_weights_t* layers_t,
                              const vt_layer_acts* acts, const vt_layer_grads* grads, int num_layers, const void* x,
                              const float* mask, int mask_additive, void* g, const vt_bwd_workspace* ws, int B, int S,
                              int H, int nh, int I, float ln_eps, int accumulate, float p_hidden, float p_attn,
                              uint64_t drop_seed, int layer0, vt_stream_t stream) {
-  return encoder_backward_impl(layers, layers_t, acts, grads, num_layers, x, mask, mask_additive, g, ws, nullptr, B, S, H,
-                               nh, I, ln_eps, accumulate, p_hidden, p_attn, drop_seed, layer0, (hipStream_t)stream, nullptr);
+  return vt_encoder_backward_dispatch(layers, layers_t, acts, grads, num_layers, x, mask, mask_additive, g, ws, nullptr, B, S,
+                                      H, nh, I, ln_eps, accumulate, p_hidden, p_attn, drop_seed, layer0, (hipStream_t)stream,
+                                      nullptr);
 }
 
 int vt_encoder_backward_overlap_bf16(const vt_layer_weights* layers, const vt_layer_weights_t* layers_t,
@@ -1156,9 +676,9 @@ int vt_encoder_backward_overlap_bf16(const vt_layer_weights* layers, const vt_la
                                      const vt_bwd_workspace* ws, const vt_bwd_workspace* ws_b, int B, int S, int H, int nh,
                                      int I, float ln_eps, int accumulate, float p_hidden, float p_attn,
                                      uint64_t drop_seed, int layer0, vt_stream_t stream, vt_stream_t side_stream) {
-  return encoder_backward_impl(layers, layers_t, acts, grads, num_layers, x, mask, mask_additive, g, ws, ws_b, B, S, H, nh,
-                               I, ln_eps, accumulate, p_hidden, p_attn, drop_seed, layer0, (hipStream_t)stream,
-                               (hipStream_t)side_stream);
+  return vt_encoder_backward_dispatch(layers, layers_t, acts, grads, num_layers, x, mask, mask_additive, g, ws, ws_b, B, S, H,
+                                      nh, I, ln_eps, accumulate, p_hidden, p_attn, drop_seed, layer0, (hipStream_t)stream,
+                                      (hipStream_t)side_stream);
 }
 
 int vt_encoder_backward_seq_bf16(const vt_layer_weights* layers, const vt_layer_weights_t* layers_t,
@@ -1168,9 +688,9 @@ int vt_encoder_backward_seq_bf16(const vt_layer_weights* layers, const vt_layer_
                                  uint64_t drop_seed, int layer0, int64_t rows, const int32_t* seq_start,
                                  const int32_t* seq_len, vt_stream_t stream, vt_stream_t side_stream) {
   if (rows <= 0) return VT_ERR_BAD_SHAPE;
-  return encoder_backward_impl(layers, layers_t, acts, grads, num_layers, x, nullptr, 0, g, ws, ws_b, B, S, H, nh, I, ln_eps,
-                               accumulate, p_hidden, p_attn, drop_seed, layer0, (hipStream_t)stream,
-                               (hipStream_t)side_stream, (long)rows, seq_start, seq_len);
+  return vt_encoder_backward_dispatch(layers, layers_t, acts, grads, num_layers, x, nullptr, 0, g, ws, ws_b, B, S, H, nh, I,
+                                      ln_eps, accumulate, p_hidden, p_attn, drop_seed, layer0, (hipStream_t)stream,
+                                      (hipStream_t)side_stream, (long)rows, seq_start, seq_len);
 }
 
-}  // extern "C"
+}  // the C ABI

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/visitron_hip.h"   // the C ABI: error codes, VT_ACT_*, the dropout sites (VT_SITE_*), VT_TUNE_KIND
+#include "per_device.hpp"
+#include "switches.hpp"
 
 typedef uint16_t bf16_t;  // raw bfloat16 bits in memory
 
@@ -279,6 +281,8 @@ __host__ __forceinline__ DropCfg vt_make_drop(float p, uint64_t step_seed, uint3
   d.scale = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
   return d;
 }
+// what a kernel is handed where a caller names no dropout: threshold 0 keeps every element
+__host__ __forceinline__ DropCfg vt_no_drop() { return DropCfg{0u, 0u, 1.0f}; }
 // ---- attention-probability dropout (oscar/modeling_bert.py:62): one hash word per FOUR neighbouring keys ------------------
 // The attention forward is bound by vector issue and half of its slots were this decision.  For the attention sites a hash
 // word serves the keys 4m .. 4m+3 of a query -- byte j against an 8-bit threshold, one SDWA byte compare each, no shifts --
@@ -358,36 +362,37 @@ __device__ __forceinline__ void vt_prefetch_role(const PrefetchArgs& a, int wg, 
 
 // ---- per-device host-side state ---------------------------------------------------------------------------
 // One process may drive several GPUs from several threads (torch.nn.DataParallel, pretrain.py:93-94): everything the
-// host side remembers between calls is kept PER DEVICE (the calling thread's current device) and behind atomics.
-#define VT_MAX_DEVICES 64
+// host side remembers between calls is kept PER DEVICE (the calling thread's current device) and behind atomics --
+// each piece a VtPerDevice<T> (per_device.hpp: VT_MAX_DEVICES slots, each built once on first use on its device).
 inline int vt_current_device() {
   int d = 0;
   return (hipGetDevice(&d) == hipSuccess && d >= 0 && d < VT_MAX_DEVICES) ? d : -1;
 }
 // compute units of the current device (0 on error)
-inline int vt_device_cus() {
-  static std::atomic<int> cus[VT_MAX_DEVICES];
-  const int d = vt_current_device();
-  if (d < 0) return 0;
-  int c = cus[d].load(std::memory_order_relaxed);
-  if (!c) {
+struct VtDeviceCus {
+  int cus = 0;
+  explicit VtDeviceCus(int dev) {
     hipDeviceProp_t p;
-    if (hipGetDeviceProperties(&p, d) != hipSuccess) return 0;
-    c = p.multiProcessorCount;
-    cus[d].store(c, std::memory_order_relaxed);
+    if (hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
   }
-  return c;
+};
+inline int vt_device_cus() {
+  static VtPerDevice<VtDeviceCus> store;
+  const VtDeviceCus* c = store.get();
+  return c ? c->cus : 0;
 }
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel call site, device): function attributes belong to
-// the device's copy of the code object, so a process-wide "done" flag would skip the second GPU.
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): function attributes belong to the device's
+// copy of the code object, so a process-wide "done" flag would skip the second GPU.  One of these sits beside each kernel
+// of a dispatch table and is set for the kernel about to be launched.
 struct VtLdsAttrOnce {
-  std::atomic<bool> done[VT_MAX_DEVICES];
+  struct Flag { std::atomic<bool> done{false}; };
+  VtPerDevice<Flag> flags;
   bool set(const void* kern, int bytes) {
-    const int d = vt_current_device();
-    if (d < 0) return false;
-    if (done[d].load(std::memory_order_acquire)) return true;
+    Flag* f = flags.get();
+    if (!f) return false;
+    if (f->done.load(std::memory_order_acquire)) return true;
     if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
-    done[d].store(true, std::memory_order_release);
+    f->done.store(true, std::memory_order_release);
     return true;
   }
 };
@@ -400,3 +405,14 @@ inline std::atomic<int>& vt_deterministic_word() {
   return on;
 }
 inline bool vt_deterministic() { return vt_deterministic_word().load(std::memory_order_relaxed) != 0; }
+// Attention-probability dropout in 16-bit fields (default since ABI 12: p in steps of 1/65536, two keys per hash word -- the
+// reference's nn.Dropout(0.1) runs as 0.100006) or 8-bit fields (rounds 4-5's form: steps of 1/256, four keys per hash word,
+// 0.1 runs as 0.1016; the attention forward is ~5 % faster, the B = 256 step 0.15 %; see vt_attn_wide above).  One word for
+// the run as well (vt_set_attn_dropout_bits; VT_ATTN_DROPOUT_BITS=8 in the environment selects the old form from the start):
+// read when a call builds its DropCfg, so forward and backward of one step must run under the same setting (set it before
+// building the engine).
+inline std::atomic<int>& vt_attn_drop_bits_word() {
+  static std::atomic<int> bits{vt_switch(VT_ATTN_DROPOUT_BITS) == 8 ? 8 : 16};
+  return bits;
+}
+inline int vt_attn_drop_bits() { return vt_attn_drop_bits_word().load(std::memory_order_relaxed); }

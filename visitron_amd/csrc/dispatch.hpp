@@ -50,6 +50,24 @@ int vt_assemble_regions_dispatch(const float* img_feats, const int64_t* region_c
                                  int64_t* labels_out, int64_t* mask_out, int64_t* token_labels_out, int B, int T, int R,
                                  int R_in, int D, hipStream_t stream);
 
+// ---- encoder_loops.hip: the encoder stack's layer loops and their weight-prefetch policy
+int vt_encoder_forward_ln_dispatch(const vt_layer_weights_ln* layers, int num_layers, void* s16_a, void* sf_a, float* stats_a,
+                                   void* s16_b, void* sf_b, float* stats_b, void* qkv, void* ctx, void* mid, const float* mask,
+                                   int mask_additive, const float* head_scale, int B, int S, int H, int nh, int I, float ln_eps,
+                                   long stat_rows, hipStream_t stream, long rows, const int* seq_start, const int* seq_len);
+int vt_encoder_forward_dispatch(const vt_layer_weights* layers, const vt_layer_acts* acts, int num_layers, const void* x,
+                                const float* mask, int mask_additive, const float* head_scale, int B, int S, int H, int nh,
+                                int I, float ln_eps, float p_hidden, float p_attn, uint64_t drop_seed, hipStream_t stream,
+                                long rows, const int* seq_start, const int* seq_len);
+int vt_encoder_backward_dispatch(const vt_layer_weights* layers, const vt_layer_weights_t* layers_t, const vt_layer_acts* acts,
+                                 const vt_layer_grads* grads, int num_layers, const void* x, const float* mask,
+                                 int mask_additive, void* g, const vt_bwd_workspace* ws_a, const vt_bwd_workspace* ws_b, int B,
+                                 int S, int H, int nh, int I, float ln_eps, int accumulate, float p_hidden, float p_attn,
+                                 uint64_t drop_seed, int layer0, hipStream_t stream, hipStream_t side, long rows = 0,
+                                 const int* seq_start = nullptr, const int* seq_len = nullptr);
+int vt_weight_prefetch_set(int training_mode, int inference_mode);
+int vt_weight_prefetch_get(int inference);
+
 // ---- fp32_path.hip: the fp32 inference path (and the fp32 training step's GEMM and LayerNorm)
 int vt_gemm_f32_dispatch(const float* A, long lda, long sA_b, long sA_h, const float* W, long ldw, long sW_b, long sW_h,
                          int w_is_kn, const float* bias, const float* R, long ldr, float* C, long ldc, long sC_b, long sC_h,
@@ -121,10 +139,10 @@ int vt_gemm_sk_counter_ptrs(unsigned** ptrs, int max);
 void vt_wgrad_set_tile(int tn);
 int vt_wgrad_dispatch(WgradArgs& a, hipStream_t stream);
 
-// ---- gemm_wgrad_v8.hip: the persistent weight-gradient kernel's switch and timeout counter
+// ---- gemm_wgrad_v8.hip: the persistent weight-gradient kernel's switch and timeout counter; the step's two counters in one launch
 void vt_wgrad_v8_enable(int on);
 int vt_wgrad_v8_timeouts(unsigned* out);
-unsigned* vt_wgrad_timeouts_devptr();
+int vt_step_counters_dispatch(long long* out2, hipStream_t stream);
 
 // ---- ln_deferred.hip: the inference path's deferred LayerNorm
 int vt_ln_apply_dispatch(const void* v, long ldv, const float* stats, int np, long stat_rows, const float* gamma,
@@ -152,6 +170,14 @@ long vt_softdot_bwd_split_ws_floats(int B, int L, int D);
 int vt_softdot_bwd_split_dispatch(const SoftDotBwdArgs& a, float* ws, hipStream_t stream);
 int vt_softdot_bwd_dispatch(const SoftDotBwdArgs& a, hipStream_t stream);
 int vt_skinny_linear_dispatch(const SkinnyArgs& a, hipStream_t stream);
+// the T steps of a sequence, one launch per position; sv_*: optional training saves laid out like the padded sequence
+int vt_lstm_sequence_dispatch(const float* xproj, long ldx_b, long ldx_t, float* h2_0, float* h2_1, float* c, const void* w_hh,
+                              const int* lengths, float* seq_out, long lds_b, long lds_t, int B, int hs, int T, int reverse,
+                              hipStream_t stream, const int* xrow_start, float* sv_gates = nullptr, float* sv_c = nullptr,
+                              void* sv_h = nullptr, long S_sv = 0);
+int vt_lstm_sequence_bwd_dispatch(const float* d_seq_out, long ldd_b, long ldd_t, const float* dh_final, float* dc,
+                                  const void* w_hh_t, const int* lengths, const float* sv_gates, const float* sv_c, void* dgates,
+                                  long S_sv, int B, int hs, int T, int reverse, hipStream_t stream);
 
 // ---- rowops.hip: LayerNorm, embeddings, losses, optimizer and the other row kernels
 int vt_layernorm_dispatch(const void* x, long ldx, void* y, long ldy, const float* gamma, const float* beta,
@@ -199,4 +225,3 @@ int vt_action_head_dispatch2(const float* z, long ldz, const long* y, int B, int
                              float* out, int dz_f32, hipStream_t stream);
 int vt_action_head_dispatch(const float* z, long ldz, const long* y, int B, int A, float grad_scale, void* dz, long lddz, int Ap,
                             float* out, hipStream_t stream);
-int vt_prefetch_dispatch(const void* const* ptrs, const long* bytes, int n, hipStream_t stream);

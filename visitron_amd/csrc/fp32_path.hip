@@ -203,7 +203,7 @@ int vt_gemm_f32_dispatch(const float* A, long lda, long sA_b, long sA_h, const f
   g.M = M; g.N = N; g.K = K; g.act = act; g.w_is_kn = w_is_kn; g.heads = heads; g.grp_rows = grp_rows; g.grp_stride = grp_stride;
   g.alpha = alpha;
   g.a_is_km = 0; g.accumulate = 0; g.split = 1; g.kchunk = (K + GF_BK - 1) / GF_BK * GF_BK; g.ws = nullptr; g.pre = nullptr;
-  g.drop.thresh = 0; g.drop.seed = 0; g.drop.scale = 1.0f;
+  g.drop = vt_no_drop();
   auto ok4 = [](const void* p, long ld, long s0, long s1) { return (((uintptr_t)p & 15) == 0) && (ld % 4 == 0) && (s0 % 4 == 0) && (s1 % 4 == 0); };
   g.vec_a = ok4(A, lda, sA_b, sA_h) ? 1 : 0;
   g.vec_w = ok4(W, ldw, sW_b, sW_h) ? 1 : 0;
@@ -399,10 +399,8 @@ __global__ __launch_bounds__(256) void layernorm_rows_f32(LnF32Args a) {
 
 int vt_layernorm_f32_dispatch(const void* x, long ldx, int x_is_f32, void* y, long ldy, int y_is_f32, const float* gamma,
                               const float* beta, long M, int H, float eps, int grp_rows, int grp_stride, hipStream_t stream) {
-  DropCfg none;
-  none.thresh = 0; none.seed = 0; none.scale = 1.0f;
-  return vt_layernorm_f32_drop_dispatch(x, ldx, x_is_f32, y, ldy, y_is_f32, gamma, beta, M, H, eps, grp_rows, grp_stride, none,
-                                        stream, 0);
+  return vt_layernorm_f32_drop_dispatch(x, ldx, x_is_f32, y, ldy, y_is_f32, gamma, beta, M, H, eps, grp_rows, grp_stride,
+                                        vt_no_drop(), stream, 0);
 }
 
 // drop_entry (vt_layernorm_drop_f32): x rows compact, y rows remapped; 0 (vt_layernorm_rows): both remapped (in place)

@@ -701,33 +701,31 @@ void vt_gemm_set_variant(int v) {
 }
 
 // Shape -> variant table filled by the host-side autotuner (visitron_amd.ops.autotune_linear) before
-// the shapes are used; read-only afterwards.  One table PER DEVICE (the calling thread's current device), guarded by a
-// mutex: threads driving different GPUs of one process (torch.nn.DataParallel) tune and look up independently.
+// the shapes are used; read-only afterwards.  One table PER DEVICE (the calling thread's current device), each guarded by
+// its own mutex: threads driving different GPUs of one process (torch.nn.DataParallel) tune and look up independently.
 // The key is (M, N, K, what the epilogue does): kind = act | residual << 4 | second output << 5 | fp32 output << 6 |
 // deferred-LayerNorm mode << 8 -- a plain dgrad and the out-proj with its residual are the same (M, N, K, act) and not
 // the same kernel time (VT_TUNE_KIND of include/visitron_hip.h is what vt_gemm_dispatch looks up; vt_gemm_tune takes the same number).
 struct TuneEntry { int M, N, K, kind, variant; };
-struct TuneTable { TuneEntry e[512]; int n; };
-static TuneTable g_tune_dev[VT_MAX_DEVICES];
-static std::mutex g_tune_mu;
+struct TuneTable { std::mutex mu; TuneEntry e[512]; int n = 0; };
+static VtPerDevice<TuneTable> g_tune_dev;
 void vt_gemm_tune_set(int M, int N, int K, int kind, int variant) {
-  const int dev = vt_current_device();
-  if (dev < 0) return;
-  std::lock_guard<std::mutex> lock(g_tune_mu);
-  TuneEntry* g_tune = g_tune_dev[dev].e;
-  int& g_ntune = g_tune_dev[dev].n;
+  TuneTable* t = g_tune_dev.get();
+  if (!t) return;
+  std::lock_guard<std::mutex> lock(t->mu);
+  TuneEntry* g_tune = t->e;
+  int& g_ntune = t->n;
   for (int i = 0; i < g_ntune; ++i)
     if (g_tune[i].M == M && g_tune[i].N == N && g_tune[i].K == K && g_tune[i].kind == kind) { g_tune[i].variant = variant; return; }
   if (g_ntune < 512) g_tune[g_ntune++] = TuneEntry{M, N, K, kind, variant};
 }
 // ln_only: the caller can only run the 256x256-tile kernels (deferred-LayerNorm epilogues)
 int vt_gemm_pick_variant(int M, int N, int K, int kind) {
-  const int dev = vt_current_device();
   const bool ln_only = (kind >> 8) != 0;
-  {
-    std::lock_guard<std::mutex> lock(g_tune_mu);
-    const TuneEntry* g_tune = g_tune_dev[dev < 0 ? 0 : dev].e;
-    const int g_ntune = dev < 0 ? 0 : g_tune_dev[dev].n;
+  if (TuneTable* t = g_tune_dev.get()) {
+    std::lock_guard<std::mutex> lock(t->mu);
+    const TuneEntry* g_tune = t->e;
+    const int g_ntune = t->n;
     for (int i = 0; i < g_ntune; ++i)
       if (g_tune[i].M == M && g_tune[i].N == N && g_tune[i].K == K && g_tune[i].kind == kind) return g_tune[i].variant;
     // a row count the tuner has not seen (compacted batches change it every step): the entry of the same (N, K, kind)

@@ -22,30 +22,42 @@ int vt_gemm_persistent_cus() {
 // = 8 x 32 workgroup slots x 256 KiB of fp32 accumulators, then 256 arrival counters and one error counter (the
 // caller hands the memory over ZEROED; the kernels leave the counters at zero).  Regions alternate per launch (one counter for
 // all devices and streams); only launches of ONE stream are ordered against the reuse of a region.
-struct SkWorkspace { char* base; int regions; };
-static SkWorkspace g_sk_ws[VT_MAX_DEVICES];
+struct SkWorkspace {
+  std::atomic<char*> base{nullptr};
+  std::atomic<int> regions{0};
+  // the error counter at the end of region r
+  unsigned* err(int r) const { return (unsigned*)(base.load(std::memory_order_relaxed) + (long)(r + 1) * V8_SK_REGION_BYTES - 4096 + 2048); }
+};
+static VtPerDevice<SkWorkspace> g_sk_ws;
 static std::atomic<unsigned> g_sk_ctr{0};
+// the current device's workspace where one is registered, else null
+static SkWorkspace* sk_workspace() {
+  SkWorkspace* w = g_sk_ws.get();
+  return w && w->regions.load(std::memory_order_acquire) > 0 ? w : nullptr;
+}
+// the region of the next launch
+static char* sk_next_region(SkWorkspace* w) {
+  return w->base.load(std::memory_order_relaxed) +
+         (long)(g_sk_ctr.fetch_add(1) % (unsigned)w->regions.load(std::memory_order_relaxed)) * V8_SK_REGION_BYTES;
+}
 int vt_gemm_set_workspace_impl(void* base, long bytes) {
-  const int dev = vt_current_device();
-  if (dev < 0 || dev >= VT_MAX_DEVICES) return VT_ERR_HIP;
+  SkWorkspace* w = g_sk_ws.get();
+  if (!w) return VT_ERR_HIP;
   if (base && (((uintptr_t)base & 255) || bytes < V8_SK_REGION_BYTES)) return VT_ERR_BAD_ALIGN;
-  g_sk_ws[dev].base = (char*)base;
-  g_sk_ws[dev].regions = base ? (int)(bytes / V8_SK_REGION_BYTES) : 0;
+  w->base.store((char*)base, std::memory_order_relaxed);
+  w->regions.store(base ? (int)(bytes / V8_SK_REGION_BYTES) : 0, std::memory_order_release);
   return VT_OK;
 }
 long vt_gemm_workspace_region_bytes_impl() { return V8_SK_REGION_BYTES; }
-int vt_gemm_has_workspace() {
-  const int dev = vt_current_device();
-  return dev >= 0 && dev < VT_MAX_DEVICES && g_sk_ws[dev].regions > 0;
-}
+int vt_gemm_has_workspace() { return sk_workspace() != nullptr; }
 // Sum of the regions' error counters (bounded waits of a finishing workgroup that ran out), cleared on read.  Blocking.
 int vt_gemm_shared_tile_timeouts_impl(unsigned* out) {
   *out = 0;
-  const int dev = vt_current_device();
-  if (dev < 0 || dev >= VT_MAX_DEVICES || g_sk_ws[dev].regions <= 0) return VT_OK;
-  for (int r = 0; r < g_sk_ws[dev].regions; ++r) {
+  SkWorkspace* w = sk_workspace();
+  if (!w) return VT_OK;
+  for (int r = 0; r < w->regions.load(std::memory_order_relaxed); ++r) {
     unsigned v = 0;
-    char* p = g_sk_ws[dev].base + (long)(r + 1) * V8_SK_REGION_BYTES - 4096 + 2048;
+    unsigned* p = w->err(r);
     if (hipMemcpy(&v, p, 4, hipMemcpyDeviceToHost) != hipSuccess) return VT_ERR_HIP;
     if (v) {
       const unsigned zero = 0;
@@ -57,19 +69,18 @@ int vt_gemm_shared_tile_timeouts_impl(unsigned* out) {
 }
 // the regions' error counters on the current device (vt_step_counters): how many, at most `max`
 int vt_gemm_sk_counter_ptrs(unsigned** ptrs, int max) {
-  const int dev = vt_current_device();
-  if (dev < 0 || dev >= VT_MAX_DEVICES || g_sk_ws[dev].regions <= 0) return 0;
+  SkWorkspace* w = sk_workspace();
+  if (!w) return 0;
   int n = 0;
-  for (int r = 0; r < g_sk_ws[dev].regions && n < max; ++r)
-    ptrs[n++] = (unsigned*)(g_sk_ws[dev].base + (long)(r + 1) * V8_SK_REGION_BYTES - 4096 + 2048);
+  for (int r = 0; r < w->regions.load(std::memory_order_relaxed) && n < max; ++r) ptrs[n++] = w->err(r);
   return n;
 }
 // fills the shared-tile fields of a launch's arguments; false: no workspace on this device
 static bool v8_take_region(GemmArgs& g) {
-  const int dev = vt_current_device();
-  if (dev < 0 || dev >= VT_MAX_DEVICES || g_sk_ws[dev].regions <= 0) return false;
+  SkWorkspace* w = sk_workspace();
+  if (!w) return false;
   static const int parts_env = (int)vt_switch(VT_GEMM_SK);   // 0 / 1: the region off
-  char* reg = g_sk_ws[dev].base + (long)(g_sk_ctr.fetch_add(1) % (unsigned)g_sk_ws[dev].regions) * V8_SK_REGION_BYTES;
+  char* reg = sk_next_region(w);
   g.sk_ws = (float*)reg;
   g.sk_sem = (int*)(reg + V8_SK_REGION_BYTES - 4096);
   g.sk_err = (unsigned*)(reg + V8_SK_REGION_BYTES - 4096 + 2048);
@@ -79,9 +90,9 @@ static bool v8_take_region(GemmArgs& g) {
 int vt_gemm_v8_take_region(GemmArgs& g) { return v8_take_region(g) ? 1 : 0; }   // gemm_v7_ln.hip
 // one region of the workspace as plain scratch (the split-K planes of variant 33, gemm_bf16.hip); null: none / too small
 void* vt_gemm_take_scratch(long bytes) {
-  const int dev = vt_current_device();
-  if (dev < 0 || dev >= VT_MAX_DEVICES || g_sk_ws[dev].regions <= 0 || bytes > V8_SK_REGION_BYTES - 4096) return nullptr;
-  return g_sk_ws[dev].base + (long)(g_sk_ctr.fetch_add(1) % (unsigned)g_sk_ws[dev].regions) * V8_SK_REGION_BYTES;
+  SkWorkspace* w = sk_workspace();
+  if (!w || bytes > V8_SK_REGION_BYTES - 4096) return nullptr;
+  return sk_next_region(w);
 }
 
 // Workgroups of a persistent launch: one per CU at most.  The stream-K region (sk_parts > 1) spreads a chunk's tiles over every

@@ -178,6 +178,61 @@ int vt_lstm_step_bwd_dispatch(const LstmBwdArgs& a, hipStream_t stream) {
   return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
 }
 
+// The T steps of a sequence, one launch per position.  sv_*: optional training saves laid out like the padded sequence,
+// [B, S_sv, .] (position t of row b at (b * S_sv + t))
+int vt_lstm_sequence_dispatch(const float* xproj, long ldx_b, long ldx_t, float* h2_0, float* h2_1, float* c, const void* w_hh,
+                              const int* lengths, float* seq_out, long lds_b, long lds_t, int B, int hs, int T, int reverse,
+                              hipStream_t stream, const int* xrow_start, float* sv_gates, float* sv_c, void* sv_h, long S_sv) {
+  if (!xproj || !h2_0 || !h2_1 || !c || !w_hh) return VT_ERR_NULL;
+  if (T <= 0) return VT_ERR_BAD_SHAPE;
+  if (xrow_start && !lengths) return VT_ERR_NULL;   // compacted rows exist only below a sequence's length
+  if (sv_gates && (!sv_c || !sv_h || S_sv < T)) return VT_ERR_BAD_SHAPE;
+  float* hb[2] = {h2_0, h2_1};
+  for (int i = 0; i < T; ++i) {
+    const int t = reverse ? T - 1 - i : i;
+    LstmStepArgs a;
+    a.xrow_start = xrow_start; a.ldx_row = ldx_t;
+    a.xproj = xrow_start ? xproj : xproj + (int64_t)t * ldx_t; a.ldx = ldx_b; a.h_prev = hb[i & 1]; a.h_out = hb[(i + 1) & 1]; a.c = c;
+    a.w_hh = (const bf16_t*)w_hh; a.lengths = lengths; a.seq_out = seq_out ? seq_out + (int64_t)t * lds_t : nullptr;
+    a.ld_seq = lds_b; a.B = B; a.hs = hs; a.t = t;
+    a.sv_gates = sv_gates ? sv_gates + (int64_t)t * 4 * hs : nullptr; a.ld_svg = S_sv * 4 * hs;
+    a.sv_c = sv_gates ? sv_c + (int64_t)t * hs : nullptr; a.ld_svc = S_sv * hs;
+    a.sv_h = sv_gates ? (bf16_t*)sv_h + (int64_t)t * hs : nullptr; a.ld_svh = S_sv * hs;
+    const int rc = vt_lstm_step_dispatch(a, stream);
+    if (rc != VT_OK) return rc;
+  }
+  if (T & 1) {
+    if (hipMemcpyAsync(h2_0, h2_1, (size_t)B * hs * sizeof(float), hipMemcpyDeviceToDevice, stream) != hipSuccess)
+      return VT_ERR_HIP;
+  }
+  return VT_OK;
+}
+
+// Back-propagation through the T steps of a training sequence, in the reverse of the order they ran.  d_seq_out
+// [B, ., hs] (strides ldd_b, ldd_t; may be null), dh_final / dc [B, hs] (dc: in = gradient of the final cell state, it is
+// the running value afterwards), saves and dgates [B, S_sv, .]; dgates must arrive zeroed at positions >= T.
+int vt_lstm_sequence_bwd_dispatch(const float* d_seq_out, long ldd_b, long ldd_t, const float* dh_final, float* dc,
+                                  const void* w_hh_t, const int* lengths, const float* sv_gates, const float* sv_c, void* dgates,
+                                  long S_sv, int B, int hs, int T, int reverse, hipStream_t stream) {
+  if (!dc || !w_hh_t || !sv_gates || !sv_c || !dgates) return VT_ERR_NULL;
+  if (T <= 0 || S_sv < T) return VT_ERR_BAD_SHAPE;
+  bf16_t* dg = (bf16_t*)dgates;
+  for (int i = T - 1; i >= 0; --i) {
+    const int t = reverse ? T - 1 - i : i;                     // the forward's i-th step ran position t
+    const int t_next = (i == T - 1) ? -1 : (reverse ? t - 1 : t + 1);
+    LstmBwdArgs a;
+    a.dg_next = t_next < 0 ? nullptr : dg + (int64_t)t_next * 4 * hs; a.ld_dgn = S_sv * 4 * hs;
+    a.w_hh_t = (const bf16_t*)w_hh_t; a.dh_final = dh_final;
+    a.d_out = d_seq_out ? d_seq_out + (int64_t)t * ldd_t : nullptr; a.ld_dout = ldd_b; a.dc = dc;
+    a.sv_gates = sv_gates + (int64_t)t * 4 * hs; a.ld_svg = S_sv * 4 * hs; a.sv_c = sv_c + (int64_t)t * hs; a.ld_svc = S_sv * hs;
+    a.dg_out = dg + (int64_t)t * 4 * hs; a.ld_dg = S_sv * 4 * hs; a.dg_out_f32 = nullptr; a.ld_dgf = 0;
+    a.lengths = lengths; a.B = B; a.hs = hs; a.t = t; a.t_next = t_next;
+    const int rc = vt_lstm_step_bwd_dispatch(a, stream);
+    if (rc != VT_OK) return rc;
+  }
+  return VT_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // SoftDotAttention.forward (agent_models.py:328-357) after linear_in:
 //   attn[b, l] = context[b, l, :] . target[b, :]                     (:338, torch.bmm)

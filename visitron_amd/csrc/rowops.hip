@@ -399,7 +399,7 @@ int vt_embed_layernorm_dispatch(const int64_t* ids, const int64_t* type_ids, con
   a.ids = ids; a.type_ids = type_ids; a.pos_ids = pos_ids; a.word = word; a.pos = pos; a.type = type;
   a.gamma = gamma; a.beta = beta; a.y = (bf16_t*)y; a.ldy = ldy; a.B = B; a.T = T; a.S = S; a.H = H;
   a.n_word = n_word; a.n_pos = n_pos; a.n_type = n_type; a.eps = eps; a.err = err_flag;
-  if (drop) a.drop = *drop; else { a.drop.thresh = 0; a.drop.seed = 0; a.drop.scale = 1.0f; }
+  a.drop = drop ? *drop : vt_no_drop();
   const dim3 grid((B * T + 3) / 4), block(256);
   const int ch = (H + 511) / 512;
   if (ch == 1) hipLaunchKernelGGL(embed_layernorm<1>, grid, block, 0, stream, a);
@@ -803,7 +803,7 @@ int vt_layernorm_bwd_dispatch(const void* x, long ldx, const void* dy, long ldy,
   a.x = (const bf16_t*)x; a.ldx = ldx; a.dy = (const bf16_t*)dy; a.ldy = ldy; a.gamma = gamma;
   a.dx = (bf16_t*)dx; a.lddx = lddx; a.partial = partial_ws; a.M = M; a.H = H; a.eps = eps;
   a.dx2 = (bf16_t*)dx2; a.lddx2 = lddx2;
-  if (drop) a.drop = *drop; else { a.drop.thresh = 0; a.drop.seed = 0; a.drop.scale = 1.0f; }
+  a.drop = drop ? *drop : vt_no_drop();
   if (dx2 && ((lddx2 % 8) || ((uintptr_t)dx2 & 15))) return VT_ERR_BAD_ALIGN;
   int nblocks = (M + 3) / 4;
   if (nblocks > LN_BWD_MAX_BLOCKS) nblocks = LN_BWD_MAX_BLOCKS;
@@ -1021,7 +1021,7 @@ int vt_embed_layernorm_bwd_dispatch(const int64_t* ids, const int64_t* type_ids,
   a.ids = ids; a.type_ids = type_ids; a.pos_ids = pos_ids; a.word = word; a.pos = pos; a.type = type; a.gamma = gamma;
   a.g = (const bf16_t*)g; a.ldg = ldg; a.de = de; a.partial = partial_ws; a.B = B; a.T = T; a.S = S; a.H = H;
   a.n_word = n_word; a.n_pos = n_pos; a.n_type = n_type; a.eps = eps;
-  if (drop) a.drop = *drop; else { a.drop.thresh = 0; a.drop.seed = 0; a.drop.scale = 1.0f; }
+  a.drop = drop ? *drop : vt_no_drop();
   long nb = ((long)B * T + 3) / 4;
   const int nblocks = (int)(nb > LN_BWD_MAX_BLOCKS ? LN_BWD_MAX_BLOCKS : nb);
   if (H <= 512) hipLaunchKernelGGL(embed_layernorm_bwd<1>, dim3(nblocks), dim3(256), 0, stream, a);
@@ -1989,30 +1989,3 @@ int vt_action_head_dispatch(const float* z, long ldz, const long* y, int B, int 
 // alone does not; reading W2 once before FFN-up gives the 12 us back).  This kernel reads up to four byte ranges and drops
 // the data: what it leaves behind is the lines in the Infinity Cache (and in the L2 of the XCD that happened to read them).
 __global__ __launch_bounds__(256) void prefetch_ranges(PrefetchArgs a) { vt_prefetch_role(a, blockIdx.x, gridDim.x); }
-
-// host side: the ranges a caller names (null / empty ones dropped), and how many workgroups they are worth
-static bool prefetch_pack(const void* const* ptrs, const long* bytes, int n, PrefetchArgs& a, long& wgs) {
-  long total = 0;
-  a.n = 0;
-  for (int i = 0; i < n && i < 4; ++i) {
-    if (!ptrs[i] || bytes[i] <= 0 || ((uintptr_t)ptrs[i] & 15)) continue;
-    a.p[a.n] = ptrs[i];
-    a.bytes[a.n] = bytes[i];
-    total += bytes[i];
-    ++a.n;
-  }
-  for (int i = a.n; i < 4; ++i) { a.p[i] = nullptr; a.bytes[i] = 0; }
-  wgs = (total + 16383) >> 14;
-  return a.n > 0;
-}
-
-int vt_prefetch_dispatch(const void* const* ptrs, const long* bytes, int n, hipStream_t stream) {
-  if (n <= 0) return VT_OK;
-  if (n > 4 || !ptrs || !bytes) return VT_ERR_BAD_SHAPE;
-  PrefetchArgs a;
-  long grid;
-  if (!prefetch_pack(ptrs, bytes, n, a, grid)) return VT_OK;
-  grid = grid < 1 ? 1 : (grid > 1024 ? 1024 : grid);
-  hipLaunchKernelGGL(prefetch_ranges, dim3((unsigned)grid), dim3(256), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
-}

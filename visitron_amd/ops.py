@@ -1098,13 +1098,15 @@ def attn_drop_p(p):
 
 
 def set_weight_prefetch(training=-1, inference=-1):
-    """The layer loops' weight prefetch (include/visitron_hip.h, vt_set_weight_prefetch): training 0 off .. 4 riding in the
-    LayerNorm kernels (default), inference 0 off .. 3 riding in the attention kernel (default); -1 keeps a setting."""
+    """The layer loops' weight prefetch (include/visitron_hip.h, vt_set_weight_prefetch): training 0 off or 4 riding in the
+    LayerNorm kernels (default), inference 0 off or 3 riding in the attention kernel (default); -1 keeps a setting.  Any other
+    number is refused (RuntimeError) and changes nothing."""
     _lib.check(_lib.load().vt_set_weight_prefetch(int(training), int(inference)), "vt_set_weight_prefetch")
 
 
 def weight_prefetch():
-    """(training mode, inference mode) in force."""
+    """(training mode, inference mode) in force: 0 / 4 and 0 / 3, or the number VT_PREFETCH_WEIGHTS / VT_PREFETCH_INFER named
+    (one that is not a mode runs as off)."""
     lib = _lib.load()
     return int(lib.vt_get_weight_prefetch(0)), int(lib.vt_get_weight_prefetch(1))
 
