@@ -364,6 +364,20 @@ int vt_multi_sumsq(const uint64_t* table, int64_t n_chunks, void* partials, vt_s
 int vt_norm_finish(const void* partials, int64_t n_chunks, float max_norm, float* out, vt_stream_t stream);
 /* g *= *coef_dev over the table. */
 int vt_multi_scale(const uint64_t* table, int64_t n_chunks, const float* coef_dev, vt_stream_t stream);
+/* ---- AdamW sharded over data-parallel ranks (ABI 17) --------------------------------------------------------------------
+ * DDP's gradient all-reduce (pretrain.py:96-102,191) is a reduce-scatter plus an all-gather; with the update between the
+ * two halves each rank runs AdamW.step() (pretrain.py:192) on its 1 / world of the flat slabs only.  Both entry points are
+ * one kernel launch over a chunk table in device memory, whatever the number of pieces the rank owns; host_table is the
+ * HOST copy of the same words, which the entry point checks before it launches (nothing is launched on an error).
+ * vt_shard_adamw: 7 uint64 per chunk -- byte addresses of the chunk's first p, g, m, v (p, m, v fp32, 16-byte aligned; g
+ * fp32 16-byte aligned, or with g_is_bf16 bf16 8-byte aligned) and mirror (bf16, 8-byte aligned) element, the element count
+ * (a multiple of 4; the caller cuts long segments so that the workgroups, which stride over the chunks, balance) and a
+ * decay flag (0: the update runs with wd = 0).  The arithmetic and the constants are vt_adamw_flat's, bit for bit. */
+int vt_shard_adamw(const uint64_t* table, const uint64_t* host_table, int64_t n_chunks, int g_is_bf16, float lr,
+                   float step_size, float b1, float b2, float eps, float wd, float grad_scale, vt_stream_t stream);
+/* vt_shard_settle: 4 uint64 per chunk -- addresses of p (fp32, 16-byte aligned) and mirror (bf16, 8-byte aligned), the
+ * element count (a multiple of 4) and a direction: 0: p = float(mirror), 1: mirror = bf16(p) (round to nearest even). */
+int vt_shard_settle(const uint64_t* table, const uint64_t* host_table, int64_t n_chunks, vt_stream_t stream);
 /* out[r, 64 h + d] = x[r, 64 h + d] * head_scale[h] (bf16 rows of nh * 64 columns): the reference's head_mask
  * (oscar/modeling_bert.py:65-66) on a context tensor or, on the way back, on its gradient (training path). */
 int vt_scale_heads_bf16(const void* x, int64_t ldx, void* out, int64_t ldo, int64_t rows, int nh, const float* head_scale,

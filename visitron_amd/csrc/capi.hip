@@ -21,7 +21,7 @@ const char* vt_error_string(int code) {
   }
 }
 
-int vt_abi_version(void) { return 16; }
+int vt_abi_version(void) { return 17; }
 
 // deterministic training mode (common.hpp): one word for the process, read by every dispatch at launch time
 void vt_set_deterministic(int on) { vt_deterministic_word().store(on ? 1 : 0, std::memory_order_relaxed); }
@@ -209,6 +209,17 @@ int vt_norm_finish(const void* partials, int64_t n_chunks, float max_norm, float
 
 int vt_multi_scale(const uint64_t* table, int64_t n_chunks, const float* coef_dev, vt_stream_t stream) {
   return vt_multi_scale_dispatch(table, n_chunks, coef_dev, (hipStream_t)stream);
+}
+
+// ---- AdamW sharded over data-parallel ranks (ABI 17) ------------------------------------------------------------------
+int vt_shard_adamw(const uint64_t* table, const uint64_t* host_table, int64_t n_chunks, int g_is_bf16, float lr,
+                   float step_size, float b1, float b2, float eps, float wd, float grad_scale, vt_stream_t stream) {
+  return vt_shard_adamw_dispatch(table, host_table, n_chunks, g_is_bf16, lr, step_size, b1, b2, eps, wd, grad_scale,
+                                 (hipStream_t)stream);
+}
+
+int vt_shard_settle(const uint64_t* table, const uint64_t* host_table, int64_t n_chunks, vt_stream_t stream) {
+  return vt_shard_settle_dispatch(table, host_table, n_chunks, (hipStream_t)stream);
 }
 
 int vt_mask_tokens(const int64_t* input_ids, const uint8_t* special_mask, const int64_t* token_classes, const float* u_mask,

@@ -43,6 +43,21 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
 __device__ __forceinline__ float bf16lo(uint32_t w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf16hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
 
+// Four elements of the fused AdamW (pytorch-transformers rule; see adamw_flat in rowops.hip): THE element arithmetic of the
+// whole-slab kernel and of the sharded one (shard_adamw, optim.hip) -- one text, so the two leave the same bits.
+__device__ __forceinline__ void adamw_flat_x4(f32x4& pv, const f32x4 gv, f32x4& mv, f32x4& vv, float lr, float step_size,
+                                              float b1, float b2, float eps, float wd, float grad_scale) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float gg = gv[k] * grad_scale;
+    mv[k] = b1 * mv[k] + (1.0f - b1) * gg;
+    vv[k] = b2 * vv[k] + (1.0f - b2) * gg * gg;
+    float x = pv[k] - step_size * (mv[k] / (sqrtf(vv[k]) + eps));
+    if (wd > 0.f) x = x - lr * wd * x;
+    pv[k] = x;
+  }
+}
+
 // ---- fp16 (the higher-precision copies of the residual stream: 11 significant bits against bf16's 8) ----------------
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float f16lo(uint32_t w) { return (float)__builtin_bit_cast(f16x2_t, w)[0]; }

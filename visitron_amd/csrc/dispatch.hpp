@@ -161,6 +161,10 @@ int vt_multi_adam_dispatch(const uint64_t* table, long n_chunks, const float* hy
 int vt_multi_sumsq_dispatch(const uint64_t* table, long n_chunks, void* partials, hipStream_t stream);
 int vt_norm_finish_dispatch(const void* partials, long n_chunks, float max_norm, float* out, hipStream_t stream);
 int vt_multi_scale_dispatch(const uint64_t* table, long n_chunks, const float* coef_dev, hipStream_t stream);
+// ... and the optimizer sharded over data-parallel ranks: AdamW on this rank's segments, then the non-owned segments settled
+int vt_shard_adamw_dispatch(const uint64_t* table, const uint64_t* host_table, long n_chunks, int g_is_bf16, float lr,
+                            float step_size, float b1, float b2, float eps, float wd, float grad_scale, hipStream_t stream);
+int vt_shard_settle_dispatch(const uint64_t* table, const uint64_t* host_table, long n_chunks, hipStream_t stream);
 
 // ---- rollout.hip
 int vt_lstm_step_dispatch(const LstmStepArgs& a, hipStream_t stream);

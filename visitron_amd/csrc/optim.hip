@@ -16,6 +16,8 @@ namespace {
 
 constexpr int kEntry = VT_OPTIM_ENTRY_WORDS;
 constexpr int kHyper = VT_OPTIM_HYPER_FLOATS;
+constexpr int kShardAdamWords = 7;     // vt_shard_adamw's table entry (include/visitron_hip.h)
+constexpr int kShardSettleWords = 4;   // vt_shard_settle's
 constexpr int kThreads = 256;
 constexpr int kMaxGrid = 2048;   // 256 CUs x 8 workgroups of 256 threads: a memory-bound kernel gains nothing beyond
 
@@ -156,11 +158,115 @@ __global__ __launch_bounds__(kThreads) void multi_scale(const uint64_t* __restri
   }
 }
 
+// ---- the optimizer sharded over data-parallel ranks: this rank's segments of the flat slabs -----------------------------
+// Chunk table of kShardAdamWords uint64 per entry:
+//   [0] p  [1] g  [2] m  [3] v  [4] mirror   byte addresses (p, m, v fp32; g fp32 or bf16; mirror bf16)
+//   [5] n                                    elements, a multiple of 4
+//   [6] decay                                non-zero: the chunk lies in the weight-decay group
+// m and v point into the rank's shard-sized moment storage, the rest into the full slabs.  A lane moves 16 bytes of every
+// fp32 operand and 8 bytes of every bf16 one; the element arithmetic is adamw_flat's own (adamw_flat_x4, common.hpp), so a
+// sharded step leaves the bits the whole-slab launch leaves.
+template <bool G16>
+__global__ __launch_bounds__(kThreads) void shard_adamw(const uint64_t* __restrict__ table, long n_chunks, float lr,
+                                                        float step_size, float b1, float b2, float eps, float wd,
+                                                        float grad_scale) {
+  for (long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    const uint64_t* e = table + c * kShardAdamWords;
+    float* __restrict__ p = (float*)e[0];
+    const void* __restrict__ g = (const void*)e[1];
+    float* __restrict__ m = (float*)e[2];
+    float* __restrict__ v = (float*)e[3];
+    bf16_t* __restrict__ mirror = (bf16_t*)e[4];
+    const int n4 = (int)(e[5] >> 2);
+    const float wd_c = e[6] ? wd : 0.f;
+    for (int i = threadIdx.x; i < n4; i += kThreads) {
+      f32x4 pv = ((f32x4*)p)[i], mv = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
+      f32x4 gv;
+      if (G16) {
+        const u32x2 w = ((const u32x2*)g)[i];
+        gv = (f32x4){bf16lo(w[0]), bf16hi(w[0]), bf16lo(w[1]), bf16hi(w[1])};
+      } else {
+        gv = ((const f32x4*)g)[i];
+      }
+      adamw_flat_x4(pv, gv, mv, vv, lr, step_size, b1, b2, eps, wd_c, grad_scale);
+      ((f32x4*)p)[i] = pv;
+      ((f32x4*)m)[i] = mv;
+      ((f32x4*)v)[i] = vv;
+      u32x2 o;
+      o[0] = pack_bf16x2(pv[0], pv[1]);
+      o[1] = pack_bf16x2(pv[2], pv[3]);
+      ((u32x2*)mirror)[i] = o;
+    }
+  }
+}
+
+// After the gather: the segments this rank does not own hold the owner's bits in ONE of the two copies; the other is made
+// from it.  Chunk table of kShardSettleWords uint64: [0] p  [1] mirror  [2] n (a multiple of 4)  [3] direction --
+// 0: p = float(mirror) (the weights travelled as bf16), 1: mirror = bf16(p) (they travelled as fp32).
+__global__ __launch_bounds__(kThreads) void shard_settle(const uint64_t* __restrict__ table, long n_chunks) {
+  for (long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    const uint64_t* e = table + c * kShardSettleWords;
+    float* __restrict__ p = (float*)e[0];
+    bf16_t* __restrict__ mirror = (bf16_t*)e[1];
+    const int n4 = (int)(e[2] >> 2);
+    if (e[3] == 0) {
+      for (int i = threadIdx.x; i < n4; i += kThreads) {
+        const u32x2 w = ((const u32x2*)mirror)[i];
+        ((f32x4*)p)[i] = (f32x4){bf16lo(w[0]), bf16hi(w[0]), bf16lo(w[1]), bf16hi(w[1])};
+      }
+    } else {
+      for (int i = threadIdx.x; i < n4; i += kThreads) {
+        const f32x4 pv = ((const f32x4*)p)[i];
+        u32x2 o;
+        o[0] = pack_bf16x2(pv[0], pv[1]);
+        o[1] = pack_bf16x2(pv[2], pv[3]);
+        ((u32x2*)mirror)[i] = o;
+      }
+    }
+  }
+}
+
 unsigned grid_for(long n_chunks) { return (unsigned)(n_chunks < kMaxGrid ? n_chunks : kMaxGrid); }
 
 int launched() { return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP; }
 
 }  // namespace
+
+// The tables live in device memory, so the entry points check the HOST copy the caller built them from (the same words):
+// a null or misaligned address or a count that is no multiple of 4 is refused before anything is launched.
+int vt_shard_adamw_dispatch(const uint64_t* table, const uint64_t* host_table, long n_chunks, int g_is_bf16, float lr,
+                            float step_size, float b1, float b2, float eps, float wd, float grad_scale, hipStream_t stream) {
+  if (!table || !host_table) return VT_ERR_NULL;
+  if (n_chunks <= 0) return VT_ERR_BAD_SHAPE;
+  if (((uintptr_t)table & 7) || ((uintptr_t)host_table & 7)) return VT_ERR_BAD_ALIGN;
+  for (long c = 0; c < n_chunks; ++c) {
+    const uint64_t* e = host_table + c * kShardAdamWords;
+    if (!e[0] || !e[1] || !e[2] || !e[3] || !e[4]) return VT_ERR_NULL;
+    if (e[5] == 0 || (e[5] & 3) || e[5] > (uint64_t)0x7fffffff) return VT_ERR_BAD_SHAPE;
+    if (((e[0] | e[2] | e[3]) & 15) || (e[1] & (g_is_bf16 ? 7 : 15)) || (e[4] & 7)) return VT_ERR_BAD_ALIGN;
+  }
+  if (g_is_bf16)
+    hipLaunchKernelGGL(shard_adamw<true>, dim3(grid_for(n_chunks)), dim3(kThreads), 0, stream, table, n_chunks, lr, step_size,
+                       b1, b2, eps, wd, grad_scale);
+  else
+    hipLaunchKernelGGL(shard_adamw<false>, dim3(grid_for(n_chunks)), dim3(kThreads), 0, stream, table, n_chunks, lr, step_size,
+                       b1, b2, eps, wd, grad_scale);
+  return launched();
+}
+
+int vt_shard_settle_dispatch(const uint64_t* table, const uint64_t* host_table, long n_chunks, hipStream_t stream) {
+  if (!table || !host_table) return VT_ERR_NULL;
+  if (n_chunks <= 0) return VT_ERR_BAD_SHAPE;
+  if (((uintptr_t)table & 7) || ((uintptr_t)host_table & 7)) return VT_ERR_BAD_ALIGN;
+  for (long c = 0; c < n_chunks; ++c) {
+    const uint64_t* e = host_table + c * kShardSettleWords;
+    if (!e[0] || !e[1]) return VT_ERR_NULL;
+    if (e[2] == 0 || (e[2] & 3) || e[2] > (uint64_t)0x7fffffff || e[3] > 1) return VT_ERR_BAD_SHAPE;
+    if ((e[0] & 15) || (e[1] & 7)) return VT_ERR_BAD_ALIGN;
+  }
+  hipLaunchKernelGGL(shard_settle, dim3(grid_for(n_chunks)), dim3(kThreads), 0, stream, table, n_chunks);
+  return launched();
+}
 
 int vt_multi_adam_dispatch(const uint64_t* table, long n_chunks, const float* hyper, float grad_coef,
                            const float* grad_coef_dev, hipStream_t stream) {

@@ -1058,15 +1058,7 @@ __global__ __launch_bounds__(256) void adamw_flat(float* __restrict__ p, const v
     } else {
       gv = ((const f32x4*)g)[i];
     }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float gg = gv[k] * grad_scale;
-      mv[k] = b1 * mv[k] + (1.0f - b1) * gg;
-      vv[k] = b2 * vv[k] + (1.0f - b2) * gg * gg;
-      float x = pv[k] - step_size * (mv[k] / (sqrtf(vv[k]) + eps));
-      if (wd > 0.f) x = x - lr * wd * x;
-      pv[k] = x;
-    }
+    adamw_flat_x4(pv, gv, mv, vv, lr, step_size, b1, b2, eps, wd, grad_scale);
     ((f32x4*)p)[i] = pv;
     ((f32x4*)m)[i] = mv;
     ((f32x4*)v)[i] = vv;

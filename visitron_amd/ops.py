@@ -957,6 +957,75 @@ def adamw_flat(p, g, m, v, p_bf16, lr, step_size, b1, b2, eps, wd, grad_scale=1.
     _lib.check(rc, "vt_adamw_flat")
 
 
+# ---- AdamW sharded over data-parallel ranks (visitron_amd/distributed.py: ShardPlan) ---------------------------------
+SHARD_CHUNK = 2048   # elements per table chunk: two 16-byte rounds of a workgroup; long segments and short ones then balance
+
+
+class ShardTable(object):
+    """A chunk table of vt_shard_adamw (7 words) or vt_shard_settle (4 words) on the device, with the host copy the entry
+    point checks.  rows: int64 [n, words - 2 | words - 1] of (addresses ..., elements[, flag]) per SEGMENT; segments are cut
+    here into chunks of at most `chunk` elements (a multiple of 4, so a chunk is as aligned as its segment)."""
+
+    def __init__(self, segments, elem_sizes, device, chunk=SHARD_CHUNK):
+        import numpy as np
+
+        na = len(elem_sizes)
+        seg = np.asarray(segments, dtype=np.int64).reshape(-1, na + 2)
+        assert chunk > 0 and chunk % 4 == 0
+        counts = (seg[:, na] + chunk - 1) // chunk
+        which = np.repeat(np.arange(seg.shape[0]), counts)                     # chunk -> its segment
+        first = np.cumsum(counts) - counts
+        k = np.arange(which.shape[0]) - first[which]                           # chunk -> its index inside the segment
+        tab = np.empty((which.shape[0], na + 2), dtype=np.int64)
+        for a, size in enumerate(elem_sizes):
+            tab[:, a] = seg[which, a] + k * chunk * size
+        tab[:, na] = np.minimum(seg[which, na] - k * chunk, chunk)
+        tab[:, na + 1] = seg[which, na + 1]
+        self.host = torch.from_numpy(np.ascontiguousarray(tab))
+        self.dev = self.host.to(device)
+        self.n_chunks = int(tab.shape[0])
+        self.numel = int(seg[:, na].sum())
+
+
+def shard_adamw_table(p, g, m, v, mirror, segments, chunk=SHARD_CHUNK):
+    """segments: (slab start, slab end, decay, moment offset): p, g, mirror are addressed at the slab position, m and v (the
+    rank's shard-sized moment storage) at the moment offset."""
+    _require_hip(p, g, m, v, mirror)
+    assert p.dtype == m.dtype == v.dtype == torch.float32 and mirror.dtype == BF16 and g.dtype in (torch.float32, BF16)
+    gs = g.element_size()
+    rows = [(p.data_ptr() + 4 * s, g.data_ptr() + gs * s, m.data_ptr() + 4 * mo, v.data_ptr() + 4 * mo,
+             mirror.data_ptr() + 2 * s, e - s, int(bool(dec))) for s, e, dec, mo in segments]
+    for s, e, _, mo in segments:
+        assert 0 <= s < e <= p.numel() and e <= g.numel() and e <= mirror.numel() and 0 <= mo and mo + e - s <= m.numel() == v.numel()
+    return ShardTable(rows, (4, gs, 4, 4, 2), p.device, chunk)
+
+
+def shard_settle_table(p, mirror, segments, chunk=SHARD_CHUNK):
+    """segments: (slab start, slab end, direction) -- 0: p = float(mirror), 1: mirror = bf16(p)."""
+    _require_hip(p, mirror)
+    assert p.dtype == torch.float32 and mirror.dtype == BF16
+    for s, e, _ in segments:
+        assert 0 <= s < e <= p.numel() and e <= mirror.numel()
+    rows = [(p.data_ptr() + 4 * s, mirror.data_ptr() + 2 * s, e - s, int(d)) for s, e, d in segments]
+    return ShardTable(rows, (4, 2), p.device, chunk)
+
+
+def shard_adamw(table, g_is_bf16, lr, step_size, b1, b2, eps, wd, grad_scale=1.0):
+    """adamw_flat's update on the chunks of a ShardTable (this rank's segments of the slabs), one launch."""
+    with _timed("shard_adamw", 0.0, table.numel * (28.0 if g_is_bf16 else 30.0)):
+        rc = _lib.load().vt_shard_adamw(_ptr(table.dev), _ptr(table.host), table.n_chunks, int(bool(g_is_bf16)), float(lr),
+                                        float(step_size), float(b1), float(b2), float(eps), float(wd), float(grad_scale),
+                                        _stream())
+    _lib.check(rc, "vt_shard_adamw")
+
+
+def shard_settle(table):
+    """The segments a rank does not own, after the gather: p = float(mirror) or mirror = bf16(p) per chunk, one launch."""
+    with _timed("shard_settle", 0.0, table.numel * 6.0):
+        rc = _lib.load().vt_shard_settle(_ptr(table.dev), _ptr(table.host), table.n_chunks, _stream())
+    _lib.check(rc, "vt_shard_settle")
+
+
 # ---- multi-tensor optimizer step, gradient norm and clip (visitron_amd/optim.py builds the tables) -------------------
 def multi_adam(table, n_chunks, hyper, grad_coef=1.0, grad_coef_dev=None, numel=0):
     """One launch of the Adam / AdamW rule over a chunk table (int64 [n_chunks, 6] on the device: addresses of p, g, m, v,

@@ -36,7 +36,8 @@ def _is_no_decay(name):
 class FlatParams(object):
     """Flat fp32 parameter / gradient / moment slabs + bf16 mirror for a PreTrainOscar."""
 
-    def __init__(self, model, attach_grads=True):
+    def __init__(self, model, attach_grads=True, moments=True):
+        # moments=False: no full-size m and v slabs (an engine whose optimizer is sharded over the ranks keeps shard-sized ones)
         self.attach_grads = attach_grads
         named = list(model.named_parameters())
         dev = named[0][1].device
@@ -60,8 +61,8 @@ class FlatParams(object):
         self.total = off
         self.p = torch.zeros(self.total, dtype=torch.float32, device=dev)
         self.g = torch.zeros(self.total, dtype=torch.float32, device=dev)
-        self.m = torch.zeros(self.total, dtype=torch.float32, device=dev)
-        self.v = torch.zeros(self.total, dtype=torch.float32, device=dev)
+        self.m = torch.zeros(self.total, dtype=torch.float32, device=dev) if moments else None
+        self.v = torch.zeros(self.total, dtype=torch.float32, device=dev) if moments else None
         self.mirror = torch.zeros(self.total, dtype=BF16, device=dev)
         self.off = {}
         for n, p, o, cnt, _ in self.entries:
@@ -212,9 +213,31 @@ class _State(object):
 
 
 class PretrainEngine(object):
+    """The training step of a PreTrainOscar (or of its bare trunk) on the HIP kernels; see the module docstring.
+
+    shard_optimizer=True (default False; nothing changes when it is off, and one rank runs the plain step): AdamW sharded
+    over the data-parallel ranks.  The gradient all-reduce is a reduce-scatter plus an all-gather; the update sits between
+    the halves, so each rank updates 1 / world of the slab, keeps 1 / world of the two moment slabs, and the bytes on the
+    wire stay what they were.  Ownership is static (distributed.ShardPlan); world sizes 2, 4 and 8, anything else raises
+    ValueError.  The contract, after every step, on every rank:
+      * flat.mirror is bit-identical to the replicated engine's;
+      * every parameter the step reads as fp32 (the no-decay group, the word / position / token-type tables) is exact;
+      * the parameters the step reads only through the mirror (the GEMM weights) are exact on their owner and
+        float(bf16(.)) elsewhere: a rank's parameters are always what its own forward computes with, and a later
+        refresh_mirror() from them is idempotent;
+      * consolidate() -- a COLLECTIVE every rank must call -- all-gathers the owners' fp32 values: all parameters are then
+        exact everywhere.  Required before model.state_dict() is written as a checkpoint and before fp32-route inference
+        on these weights;
+      * state_dict() is a collective too (it gathers the moments) and returns exactly the replicated engine's name-keyed
+        format; load_state_dict takes that format and keeps this rank's pieces: the two kinds of run interchange states;
+      * all_reduce_grads() raises; optimizer_step() is the un-overlapped collective (reduce-scatter, update, gather).
+    Backend nccl: reduce_scatter_tensor / all_gather_into_tensor in place on the slab; any other backend: the bucketed
+    all-reduce of the replicated step and the list form of all_gather.  Rehearsed with ranks sharing one device under
+    gloo; never run on distinct devices."""
+
     def __init__(self, model, lr=5e-5, weight_decay=0.05, eps=1e-8, betas=(0.9, 0.999), correct_bias=True,
                  schedule="linear", warmup_steps=0, t_total=20000, process_group=None, bucket_mb=64,
-                 loss_scale_by_world=True, attach_grads=True, grad_comm_dtype=None, precision="bf16"):
+                 loss_scale_by_world=True, attach_grads=True, grad_comm_dtype=None, precision="bf16", shard_optimizer=False):
         # precision: "bf16" (default: the bf16 kernels above) or "fp32" (the reference's training arithmetic: every operand,
         # activation and gradient in fp32 on the fp32 matrix cores, visitron_amd.training_f32).  Independent of
         # set_precision, which selects the inference arithmetic.
@@ -236,7 +259,6 @@ class PretrainEngine(object):
         # step actually uses is recorded in state_dict()["hyper"] and in bench.py's line, not only the configured one
         self.attention_dropout_effective = ops.attn_drop_p(float(cfg.attention_probs_dropout_prob))
         self.model, self.cfg = model, cfg
-        self.flat = FlatParams(model, attach_grads=attach_grads)
         self.lr, self.wd, self.eps, self.betas, self.correct_bias = lr, weight_decay, eps, betas, correct_bias
         self.schedule, self.warmup_steps, self.t_total = schedule, warmup_steps, t_total
         self.step_count = 0       # optimizer steps taken (Adam's t)
@@ -245,6 +267,19 @@ class PretrainEngine(object):
         self.world = 1
         if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
             self.world = torch.distributed.get_world_size(process_group)
+        # shard_optimizer: AdamW sharded over the data-parallel ranks (see the class docstring); one rank runs the plain step
+        self.shard_optimizer = bool(shard_optimizer)
+        self.shard = self.shard_optimizer and self.world > 1
+        if self.shard:
+            from .distributed import SHARD_WORLDS
+
+            if self.world not in SHARD_WORLDS:
+                raise ValueError("shard_optimizer=True serves world sizes %s (a bucket is cut into `world` pieces of whole "
+                                 "8-element groups, and %d does not divide ALIGN / 8 = %d), not %d"
+                                 % (SHARD_WORLDS, self.world, ALIGN // 8, self.world))
+        if precision == "fp32" and self.world > 1:
+            raise NotImplementedError("PretrainEngine(precision='fp32') serves one rank")
+        self.flat = FlatParams(model, attach_grads=attach_grads, moments=not self.shard)
         self.bucket_elems = int(bucket_mb * 1024 * 1024 // 4)
         self.loss_scale_by_world = loss_scale_by_world
         # data-parallel gradient exchange: the reference's DDP moves 452 MB of fp32 buckets per step (pretrain.py:96-102);
@@ -258,8 +293,6 @@ class PretrainEngine(object):
             raise ValueError("grad_comm_dtype must be 'bf16' or 'fp32'")
         self.grad_comm_dtype = grad_comm_dtype
         self.gemm_policy = "persistent GEMM on every CU (one rank, no collective beside it)"
-        if precision == "fp32" and self.world > 1:
-            raise NotImplementedError("PretrainEngine(precision='fp32') serves one rank")
         self.g16 = None
         if self.world > 1 and grad_comm_dtype == "bf16":
             self.g16 = torch.zeros(self.flat.total, dtype=BF16, device=self.flat.p.device)
@@ -299,6 +332,9 @@ class PretrainEngine(object):
             training_f32.setup(self)
         else:
             self._build_tables()
+        self.plan = None
+        if self.shard:
+            self._shard_setup()
 
     # ------------------------------------------------------------------------------ tables
     def _build_tables(self):
@@ -309,6 +345,7 @@ class PretrainEngine(object):
         self.wt_tab = (_lib.LayerWeightsT * L)()
         self.g_tab = (_lib.LayerGrads * L)()
         self._keep, self.wt = [], []
+        self._mirror_views = set()   # names of the entries the layer tables point at in the bf16 mirror
         self.layer_ranges = []   # per layer: [(start, end) in the decay region, (start, end) in the no-decay region]
         for i in range(L):
             pre = "bert.encoder.layer.%d." % i
@@ -326,8 +363,11 @@ class PretrainEngine(object):
                 ln2_g=pre + "output.LayerNorm.weight", ln2_b=pre + "output.LayerNorm.bias")
             t = dict(w_qkv=f.view(f.mirror, qw, 3 * H * H, (3 * H, H)), b_qkv=f.view(f.p, qb, 3 * H, (3 * H,)))
             gr = dict(d_w_qkv=f.view(f.g, qw, 3 * H * H, (3 * H, H)), d_b_qkv=f.view(f.g, qb, 3 * H, (3 * H,)))
+            self._mirror_views.update(pre + "attention.self.%s.weight" % x for x in ("query", "key", "value"))
             for k, n in names.items():
                 t[k] = f.view(f.mirror if k.startswith("w_") else f.p, n)
+                if k.startswith("w_"):
+                    self._mirror_views.add(n)
                 gr["d_" + k] = f.view(f.g, n)
             wt = dict(wt_qkv=torch.empty((H, 3 * H), dtype=BF16, device=f.p.device),
                       wt_ao=torch.empty((H, H), dtype=BF16, device=f.p.device),
@@ -725,14 +765,21 @@ class PretrainEngine(object):
         if comm is not None:
             # data-parallel: the head / pooler gradients are final here, before the encoder backward has started -- their
             # all-reduce goes out first and hides under the whole backward (round 3 reduced them last, with the embeddings)
-            rng = self._param_ranges([pr.transform.dense.weight, pr.transform.dense.bias, pr.transform.LayerNorm.weight,
-                                      pr.transform.LayerNorm.bias, pr.bias, lin_tok.weight, lin_tok.bias,
-                                      m.next_action.linear.weight, m.next_action.linear.bias, m.bert.pooler.dense.weight,
-                                      m.bert.pooler.dense.bias] + ([] if dec_w_is_tied else [pr.decoder.weight]))
+            rng = self._param_ranges(self._head_params())
             comm["launch"](rng)
             comm["done"].extend(rng)
         self._trunk_bwd(st, None, acc, comm, word_grad_ready=True)
         return (loss, mask_loss, next_loss, token_loss, words_acc, action_acc, token_acc)
+
+    def _head_params(self):
+        """The head / pooler parameters whose gradients are final before the encoder backward starts."""
+        m = self.model
+        pr, lin_tok = m.mlmhead.predictions, m.token_head[0]
+        tied = pr.decoder.weight is m.bert.embeddings.word_embeddings.weight
+        return [pr.transform.dense.weight, pr.transform.dense.bias, pr.transform.LayerNorm.weight,
+                pr.transform.LayerNorm.bias, pr.bias, lin_tok.weight, lin_tok.bias,
+                m.next_action.linear.weight, m.next_action.linear.bias, m.bert.pooler.dense.weight,
+                m.bert.pooler.dense.bias] + ([] if tied else [pr.decoder.weight])
 
     def _param_ranges(self, params):
         """Slab ranges [start, end) of the given parameters, ends rounded up to the alignment granule (the padding belongs
@@ -1129,7 +1176,13 @@ class PretrainEngine(object):
         invalidate_packed_weights()
 
     def optimizer_step(self, grad_scale=1.0, grads=None):
-        """AdamW.step() + scheduler.step() (pretrain.py:192-193) as two fused launches (decay / no-decay)."""
+        """AdamW.step() + scheduler.step() (pretrain.py:192-193) as two fused launches (decay / no-decay).  With the optimizer
+        sharded over several ranks it is a COLLECTIVE: reduce-scatter of the gradient slab, this rank's update, all-gather
+        of the updated weights (the sum over the ranks times grad_scale is what AdamW sees)."""
+        if self.shard:
+            if grads is not None:
+                raise ValueError("the sharded optimizer_step() reduces the gradient slab itself; it takes no `grads`")
+            return self._shard_step_unoverlapped(grad_scale)
         self._adam_ranges(self._adam_begin(), [(0, self.flat.total)], grad_scale, grads)
         self._adam_end()
 
@@ -1167,13 +1220,208 @@ class PretrainEngine(object):
         self._adam_end()
         return out
 
+    # ------------------------------------------------------------------------------ optimizer sharded over the ranks
+    def shard_atoms(self):
+        """The ranges forward_backward hands to comm["launch"] with one layer per chunk, in slab order: the heads' ranges,
+        every layer's decay and no-decay range (ends rounded up to ALIGN, as _trunk_bwd rounds them), and what is left."""
+        from .distributed import complement_ranges
+
+        f = self.flat
+        heads = self._param_ranges(self._head_params()) if self.has_heads else []
+        layers = [(lr_[k][0], min(round_up(lr_[k][1], ALIGN), f.total)) for lr_ in self.layer_ranges for k in (0, 1)]
+        return sorted(heads + layers + complement_ranges(f.total, heads + layers))
+
+    def shard_launch_ranges(self):
+        """The launches of one overlapped step with one layer per chunk, in launch order: heads, layers last first, tail."""
+        from .distributed import complement_ranges
+
+        f = self.flat
+        heads = self._param_ranges(self._head_params()) if self.has_heads else []
+        layers = [[(lr_[k][0], min(round_up(lr_[k][1], ALIGN), f.total)) for k in (0, 1)] for lr_ in reversed(self.layer_ranges)]
+        done = heads + [r_ for l_ in layers for r_ in l_]
+        return [r_ for r_ in [heads] + layers + [complement_ranges(f.total, done)] if r_]
+
+    def mirror_only_names(self):
+        """The slab entries the step reads ONLY through the bf16 mirror: what the layer tables point at in flat.mirror and
+        what the heads, the pooler and the region projection take via _mirror(...) -- minus every entry that some kernel
+        also takes as the fp32 parameter itself (the three embedding tables; the tied MLM decoder IS the word table)."""
+        m = self.model
+        via_mirror = [m.bert.pooler.dense.weight, m.bert.img_embedding.weight, m.bert.location_embeds.weight]
+        if self.has_heads:
+            via_mirror += [m.mlmhead.predictions.transform.dense.weight, m.mlmhead.predictions.decoder.weight,
+                           m.token_head[0].weight, m.next_action.linear.weight]
+        emb = m.bert.embeddings
+        as_fp32 = [emb.word_embeddings.weight, emb.position_embeddings.weight, emb.token_type_embeddings.weight]
+        names = set(self._mirror_views) | {self._name_of(p_) for p_ in via_mirror}
+        return names - {self._name_of(p_) for p_ in as_fp32}
+
+    def fp32_spans(self):
+        """Slab ranges whose updated values travel back as fp32: every entry that is not mirror-only (the whole no-decay
+        group among them), each with the padding behind it."""
+        f, only16 = self.flat, self.mirror_only_names()
+        assert not any(grp for n, _, _, _, grp in f.entries if n in only16)   # biases / LayerNorms are read as fp32
+        spans = []
+        starts = [o for _, _, o, _, _ in f.entries] + [f.total]
+        for (n, _, o, _, _), nxt in zip(f.entries, starts[1:]):
+            if n not in only16:
+                if spans and spans[-1][1] == o:
+                    spans[-1] = (spans[-1][0], nxt)
+                else:
+                    spans.append((o, nxt))
+        return spans
+
+    def shard_plan(self, world, rank, bucket_elems=None):
+        """The static ownership plan of this engine's slab for `world` ranks (any engine can compute any rank's)."""
+        from .distributed import ShardPlan
+
+        f = self.flat
+        be = self.bucket_elems if bucket_elems is None else int(bucket_elems)
+        return ShardPlan(f.total, f.n_decay, self.shard_atoms(), self.fp32_spans(), world, rank, be)
+
+    def _shard_setup(self):
+        f = self.flat
+        self.plan = self.shard_plan(self.world, torch.distributed.get_rank(self.pg))
+        # AdamW's moments of the owned pieces only, back to back in slab order (1 / world of the two slabs)
+        self.m_sh = torch.zeros(self.plan.owned, dtype=torch.float32, device=f.p.device)
+        self.v_sh = torch.zeros(self.plan.owned, dtype=torch.float32, device=f.p.device)
+        self._shard_tables = {}
+
+    def _shard_table(self, launch, grads):
+        key = (tuple(launch.ranges), grads.data_ptr())
+        tab = self._shard_tables.get(key)
+        if tab is None:
+            f = self.flat
+            tab = self._shard_tables[key] = ops.shard_adamw_table(
+                f.p, grads, self.m_sh, self.v_sh, f.mirror, [(s_, e_, dec, mo) for s_, e_, dec, _, mo in launch.own])
+        return tab
+
+    def _shard_reduce(self, launch, handles):
+        """Cast (bf16 communication copy) and reduce-scatter of one launch's ranges; returns the buffer AdamW reads."""
+        from .distributed import reduce_scatter_buckets
+
+        if self.g16 is None:
+            reduce_scatter_buckets(self.flat.g, launch, self.plan, self.bucket_elems, self.pg, handles)
+            return self.flat.g
+        for s_, e_ in launch.ranges:
+            if e_ > s_:
+                ops.cast_to_bf16(self.flat.g[s_:e_], self.g16[s_:e_])
+        reduce_scatter_buckets(self.g16, launch, self.plan, 2 * self.bucket_elems, self.pg, handles)
+        return self.g16
+
+    def _shard_update(self, consts, launch, grad_scale, grads):
+        """AdamW on this rank's segments of one launch: one kernel launch."""
+        lr, step_size, b1, b2 = consts
+        ops.shard_adamw(self._shard_table(launch, grads), grads.dtype == BF16, lr, step_size, b1, b2, self.eps, self.wd, grad_scale)
+
+    def _shard_gather(self, launch, handles):
+        """All-gather of one launch's updated pieces: the mirror where a bucket holds bf16-class elements, the fp32
+        parameters where it holds fp32-class ones."""
+        from .distributed import all_gather_buckets
+
+        f = self.flat
+        all_gather_buckets(f.mirror, [b for b in launch.buckets if b[2]], self.plan, self.pg, handles)
+        all_gather_buckets(f.p, [b for b in launch.buckets if b[3]], self.plan, self.pg, handles)
+
+    def _shard_settle(self):
+        """The segments this rank does not own, once all gathers have arrived: p = float(mirror) where the weights
+        travelled as bf16, mirror = bf16(p) where they travelled as fp32.  One launch over the whole plan."""
+        tab = self._shard_tables.get("settle")
+        if tab is None:
+            segs = [(s_, e_, int(f32)) for s_, e_, f32 in self.plan.everything().others]
+            tab = self._shard_tables["settle"] = ops.shard_settle_table(self.flat.p, self.flat.mirror, segs)
+        ops.shard_settle(tab)
+
+    def _shard_step_unoverlapped(self, grad_scale):
+        """The three phases one after the other over the whole plan (optimizer_step(), train_step(overlap=False)); the
+        launches are those of an overlapped step with one layer per chunk."""
+        launches = [self.plan.launch(r_) for r_ in self.shard_launch_ranges()]
+        handles, bufs = [], []
+        for la in launches:
+            bufs.append(self._shard_reduce(la, handles))
+        for h in handles:
+            h.wait()
+        consts = self._adam_begin()
+        for la, buf in zip(launches, bufs):
+            self._shard_update(consts, la, grad_scale, buf)
+        handles = []
+        for la in launches:
+            self._shard_gather(la, handles)
+        for h in handles:
+            h.wait()
+        self._shard_settle()
+        self._adam_end()
+
+    def _shard_train_step(self, batch, scale, layers_per_chunk, _force_comm):
+        from .distributed import complement_ranges
+
+        ws = self.world
+        handles, launched = [], []   # launched: (plan launch, gradient buffer, first handle, one past the last handle)
+
+        def reduce_ranges(rng):
+            la = self.plan.launch(rng)
+            n0 = len(handles)
+            buf = self._shard_reduce(la, handles)
+            launched.append((la, buf, n0, len(handles)))
+
+        def local_ranges(rng):   # _force_comm: the same kernels on the rank's own fp32 gradients, no collective
+            launched.append((self.plan.launch(rng), self.flat.g, 0, 0))
+            _force_comm(rng)
+
+        launch = reduce_ranges if _force_comm is None else local_ranges
+        comm = dict(layers_per_chunk=layers_per_chunk, launch=launch, done=[])
+        out = self.forward_backward(batch, grad_scale=scale, comm=comm)
+        launch(complement_ranges(self.flat.total, comm["done"]))   # embeddings, region projection
+        # per arrived range, in launch order: this rank's update, then the all-gather of that range goes out and travels
+        # while the next range is updated
+        consts = self._adam_begin()
+        gathers = []
+        for la, buf, h0, h1 in launched:
+            for h in handles[h0:h1]:
+                h.wait()
+            self._shard_update(consts, la, 1.0 / ws, buf)
+            if _force_comm is None:
+                self._shard_gather(la, gathers)
+        for h in gathers:
+            h.wait()
+        self._shard_settle()
+        self._adam_end()
+        return out
+
+    def consolidate(self):
+        """COLLECTIVE (every rank must call it): all-gather of the owners' fp32 parameters, after which flat.p -- the
+        model's parameters -- is exact on every rank.  Required before model.state_dict() is written as a checkpoint and
+        before fp32-route inference on these weights.  Nothing to do where the optimizer is not sharded."""
+        if not self.shard:
+            return
+        from .distributed import all_gather_buckets
+
+        self._require_ownership()
+        all_gather_buckets(self.flat.p, self.plan.everything().buckets, self.plan, self.pg)
+        invalidate_packed_weights()
+
+    def _shard_full_moments(self):
+        """(m, v) as full slabs on every rank: a collective gather of the shard-local storage (temporaries)."""
+        from .distributed import all_gather_buckets
+
+        every = self.plan.everything()
+        out = []
+        for sh in (self.m_sh, self.v_sh):
+            full = torch.zeros(self.flat.total, dtype=torch.float32, device=sh.device)
+            for s_, e_, _, _, mo in every.own:
+                full[s_:e_].copy_(sh[mo:mo + e_ - s_])
+            all_gather_buckets(full, every.buckets, self.plan, self.pg)
+            out.append(full)
+        return out
+
     # ------------------------------------------------------------------------------ optimizer state (resume)
     def state_dict(self):
         """What a resumed run needs beside the model's own state_dict: AdamW's moments per parameter NAME (layout-
         independent), the step / scheduler / dropout counters and the hyper-parameters.  (The reference checkpoints weights
         only, pretrain.py:247-270; this is the fused optimizer's counterpart of torch.optim's state_dict.)"""
         f = self.flat
-        state = {n: dict(exp_avg=f.view(f.m, n).detach().clone(), exp_avg_sq=f.view(f.v, n).detach().clone())
+        # (the optimizer sharded over several ranks: a COLLECTIVE -- the moments are gathered, the format is the same)
+        m_, v_ = self._shard_full_moments() if self.shard else (f.m, f.v)
+        state = {n: dict(exp_avg=f.view(m_, n).detach().clone(), exp_avg_sq=f.view(v_, n).detach().clone())
                  for n, _, _, _, _ in f.entries}
         return dict(state=state, step_count=self.step_count, sched_step=self.sched_step, fb_count=self.fb_count,
                     drop_seed_base=self.drop_seed_base,
@@ -1183,6 +1431,7 @@ class PretrainEngine(object):
                                # what travelled in the gradient all-reduce of the run that wrote this state (recorded, not
                                # restored: it is a property of the launch, and it changes the result at rounding level)
                                grad_comm_dtype=self.grad_comm_dtype, world_size=self.world, precision=self.precision,
+                               shard_optimizer=self.shard_optimizer,   # (recorded, not restored)
                                hidden_dropout=float(self.cfg.hidden_dropout_prob),
                                attention_dropout_configured=float(self.cfg.attention_probs_dropout_prob),
                                attention_dropout_effective=self.attention_dropout_effective,
@@ -1194,9 +1443,14 @@ class PretrainEngine(object):
         missing = [n for n, _, _, _, _ in f.entries if n not in sd["state"]]
         if missing:
             raise KeyError("optimizer state has no entry for %s" % ", ".join(missing[:5]))
-        for n, _, _, _, _ in f.entries:
-            f.view(f.m, n).copy_(sd["state"][n]["exp_avg"])
-            f.view(f.v, n).copy_(sd["state"][n]["exp_avg_sq"])
+        # (sharded over several ranks: the same name-keyed format goes through a full-size temporary; the rank keeps its pieces)
+        for key, slab, sh in (("exp_avg", f.m, getattr(self, "m_sh", None)), ("exp_avg_sq", f.v, getattr(self, "v_sh", None))):
+            full = torch.zeros(f.total, dtype=torch.float32, device=f.p.device) if self.shard else slab
+            for n, _, _, _, _ in f.entries:
+                f.view(full, n).copy_(sd["state"][n][key])
+            if self.shard:
+                for s_, e_, _, _, mo in self.plan.everything().own:
+                    sh[mo:mo + e_ - s_].copy_(full[s_:e_])
         self.step_count, self.sched_step = int(sd["step_count"]), int(sd["sched_step"])
         self.fb_count, self.drop_seed_base = int(sd["fb_count"]), int(sd["drop_seed_base"])
         if load_hyper:
@@ -1209,6 +1463,9 @@ class PretrainEngine(object):
         """Sum the flat gradient slab over the data-parallel group in fixed-size buckets (no overlap)."""
         if self.world == 1:
             return
+        if self.shard:
+            raise RuntimeError("with the optimizer sharded over the ranks no rank holds the whole reduced gradient slab: call "
+                               "optimizer_step(), which reduce-scatters, updates and gathers")
         from .distributed import all_reduce_flat
 
         if self.g16 is not None:
@@ -1226,6 +1483,12 @@ class PretrainEngine(object):
         scale = (1.0 / ws) if (ws > 1 and self.loss_scale_by_world) else 1.0
         if ws == 1 and _force_comm is None and overlap and self.overlap_adamw:
             return self._train_step_adamw_under_backward(batch, scale, layers_per_chunk)
+        if self.shard:
+            if overlap:
+                return self._shard_train_step(batch, scale, layers_per_chunk, _force_comm)
+            out = self.forward_backward(batch, grad_scale=scale)
+            self.optimizer_step(grad_scale=1.0 / ws)   # DDP's mean over ranks
+            return out
         if (ws == 1 and _force_comm is None) or not overlap:
             out = self.forward_backward(batch, grad_scale=scale)
             self.all_reduce_grads()
