@@ -230,6 +230,34 @@ int vt_attention_bwd_bf16(const void* qkv, int64_t ld_qkv, const void* dctx, int
                           int head_size, float drop_p, uint64_t drop_seed, uint32_t drop_site, const uint32_t* keep_bits,
                           vt_stream_t stream);
 
+/* ---- rectangular attention (ABI 18): Sq queries over Sk >= Sq keys, head size 64 ---------------------------------------------
+ * CaptionBertSelfAttention.forward with encoder_history_states (oscar/modeling_bert.py:37-41, 148-155): keys and values come
+ * from cat([history, hidden], 1), queries from the hidden positions.  qkv is the packed projection of the EXTENDED rows,
+ * bf16 [B*Sk, ld_qkv] = q | k | v: sequence b owns rows b*Sk .. b*Sk + Sk - 1, its Sh = Sk - Sq history rows first; its
+ * queries are the LAST Sq rows (the q columns of history rows are not read).  Per (b, head, query i in [0, Sq)):
+ *   ctx[b*Sq + i, h*64:(h+1)*64] = dropout(softmax_j(q_{Sh+i} . k_j / 8 + bias)) [* head_scale[h]] . v,   j over all Sk keys
+ * ctx bf16 [B*Sq, ld_ctx]; lse (optional) fp32 [B, nh, Sq].  mask (or null) with mask_additive as vt_attention_fwd_bf16, over
+ * the Sk keys: 0 = raw [B, Sk], 1 = additive [B, Sk], 2 = additive per query [B, Sq, Sk]; infinite biases as there.
+ * Dropout: the attention sites' form and resolution (vt_set_attn_dropout_bits), element index i * Sk' + j, Sk' = Sk rounded
+ * up to a multiple of 4 -- with Sq == Sk the decisions of vt_attention_fwd_bf16.  keep_bits (optional; drop_p > 0) receives
+ * them, one word per (32-query block, key): keep_bits[((b*nh + h) * nqb + qb) * kpitch + j], bit t = keep(query 32 qb + t, j),
+ * nqb = ceil(Sq / 32), kpitch = Sk rounded up to 32 (VT_KEEP_WORDS_RECT words).
+ * 1 <= Sq <= Sk <= 1024, anything else VT_ERR_UNSUPPORTED.  No workspace. */
+#define VT_KEEP_WORDS_RECT(B, nh, Sq, Sk) ((int64_t)(B) * (nh) * (((Sq) + 31) / 32) * (((Sk) + 31) / 32 * 32))
+int vt_attention_rect_fwd_bf16(const void* qkv, int64_t ld_qkv, const float* mask, int mask_additive,
+                               const float* head_scale, void* ctx, int64_t ld_ctx, float* lse, int B, int Sq, int Sk,
+                               int nh, int head_size, float drop_p, uint64_t drop_seed, uint32_t drop_site,
+                               uint32_t* keep_bits, vt_stream_t stream);
+/* Its backward (no head scale): dqkv bf16 [B*Sk, ld_dqkv] = dq | dk | dv packed like qkv.  dk and dv are written for all
+ * Sk rows of a sequence, dq for its Sq query rows, and the dq columns of its Sh history rows are written as exact zeros
+ * (the caller does not pre-fill).  dctx, ctx [B*Sq, .], lse [B, nh, Sq] as the forward left them; keep_bits: the words the
+ * forward wrote with the same drop_p / seed / site, or NULL = the decisions are taken from the hash again.  Every sum has
+ * a fixed order and there is no atomic: two runs give the same bits in any mode. */
+int vt_attention_rect_bwd_bf16(const void* qkv, int64_t ld_qkv, const void* dctx, int64_t ld_d, const void* ctx,
+                               int64_t ld_ctx, const float* mask, int mask_additive, const float* lse, void* dqkv,
+                               int64_t ld_dqkv, int B, int Sq, int Sk, int nh, int head_size, float drop_p,
+                               uint64_t drop_seed, uint32_t drop_site, const uint32_t* keep_bits, vt_stream_t stream);
+
 /* y = BertLayerNorm(x) over rows of H (biased variance, eps inside the sqrt); x already holds
  * dense(h) + bias + residual.  BertSelfOutput / BertOutput LayerNorm (called at
  * oscar/modeling_bert.py:94,120) and the optional image LayerNorm (encoder.py:280-281; use

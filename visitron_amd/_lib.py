@@ -27,7 +27,7 @@ _POINTEES = ("void", "float", "int", "int32_t", "int64_t", "uint8_t", "uint16_t"
 _classes = {}   # C struct name -> Structure class, filled by _parse_header
 # `#define VT_NAME <integer>` / `(-<integer>)` is a constant; any other #define must be one of these: the include guard, the
 # function-like macros (Python keeps its own ops.keep_words / site_* / tune_kind) and the two unsigned site numbers beside them
-_MACROS = ("VISITRON_HIP_H", "VT_KEEP_WORDS", "VT_SITE_ATTN", "VT_SITE_SELFOUT", "VT_SITE_OUT", "VT_SITE_EMB", "VT_SITE_IMG", "VT_TUNE_KIND")
+_MACROS = ("VISITRON_HIP_H", "VT_KEEP_WORDS_RECT", "VT_KEEP_WORDS","VT_SITE_ATTN", "VT_SITE_SELFOUT", "VT_SITE_OUT", "VT_SITE_EMB", "VT_SITE_IMG", "VT_TUNE_KIND")
 _DECL = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\s*)?)*)(\w+(?:\s*,\s*\w+)*)")   # [const] base [*...] name[, name]
 
 

@@ -21,7 +21,7 @@ const char* vt_error_string(int code) {
   }
 }
 
-int vt_abi_version(void) { return 17; }
+int vt_abi_version(void) { return 18; }
 
 // deterministic training mode (common.hpp): one word for the process, read by every dispatch at launch time
 void vt_set_deterministic(int on) { vt_deterministic_word().store(on ? 1 : 0, std::memory_order_relaxed); }
@@ -403,6 +403,25 @@ int vt_attention_fwd_seq_bf16(const void* qkv, int64_t ld_qkv, const float* head
   const DropCfg d = vt_make_drop_attn(drop_p, drop_seed, drop_site, vt_attn_drop_bits());
   return vt_attention_fwd_dispatch(qkv, ld_qkv, nullptr, 0, head_scale, ctx, ld_ctx, lse, B, S, nh, head_size,
                                    (hipStream_t)stream, &d, seq_start, seq_len, keep_bits);
+}
+
+int vt_attention_rect_fwd_bf16(const void* qkv, int64_t ld_qkv, const float* mask, int mask_additive, const float* head_scale,
+                               void* ctx, int64_t ld_ctx, float* lse, int B, int Sq, int Sk, int nh, int head_size, float drop_p,
+                               uint64_t drop_seed, uint32_t drop_site, uint32_t* keep_bits, vt_stream_t stream) {
+  if (!vt_attn_drop_ok(drop_p, vt_attn_drop_bits())) return VT_ERR_UNSUPPORTED;
+  const DropCfg d = vt_make_drop_attn(drop_p, drop_seed, drop_site, vt_attn_drop_bits());
+  return vt_attention_rect_fwd_dispatch(qkv, ld_qkv, mask, mask_additive, head_scale, ctx, ld_ctx, lse, B, Sq, Sk, nh, head_size,
+                                        d, keep_bits, (hipStream_t)stream);
+}
+
+int vt_attention_rect_bwd_bf16(const void* qkv, int64_t ld_qkv, const void* dctx, int64_t ld_d, const void* ctx, int64_t ld_ctx,
+                               const float* mask, int mask_additive, const float* lse, void* dqkv, int64_t ld_dqkv, int B,
+                               int Sq, int Sk, int nh, int head_size, float drop_p, uint64_t drop_seed, uint32_t drop_site,
+                               const uint32_t* keep_bits, vt_stream_t stream) {
+  if (!vt_attn_drop_ok(drop_p, vt_attn_drop_bits())) return VT_ERR_UNSUPPORTED;
+  const DropCfg d = vt_make_drop_attn(drop_p, drop_seed, drop_site, vt_attn_drop_bits());
+  return vt_attention_rect_bwd_dispatch(qkv, ld_qkv, dctx, ld_d, ctx, ld_ctx, mask, mask_additive, lse, dqkv, ld_dqkv, B, Sq, Sk,
+                                        nh, head_size, d, keep_bits, (hipStream_t)stream);
 }
 
 int vt_attention_probs_f32(const void* qkv, int64_t ld_qkv, const float* mask, int mask_additive, const float* head_scale,

@@ -39,6 +39,15 @@ int vt_attention_fwd_dispatch(const void* qkv, long ld_qkv, const float* mask, i
 int vt_attention_probs_dispatch(const void* qkv, long ld_qkv, const float* mask, int mask_additive, const float* head_scale,
                                 const float* lse, float* probs, int B, int S, int nh, int head_size, hipStream_t stream);
 
+// ---- attention_rect.hip: Sq queries over Sk >= Sq keys (encoder_history_states)
+int vt_attention_rect_fwd_dispatch(const void* qkv, long ld_qkv, const float* mask, int mask_mode, const float* head_scale,
+                                   void* ctx, long ld_ctx, float* lse, int B, int Sq, int Sk, int nh, int head_size,
+                                   const DropCfg& drop, uint32_t* keep_bits, hipStream_t stream);
+int vt_attention_rect_bwd_dispatch(const void* qkv, long ld_qkv, const void* dctx, long ld_d, const void* ctx, long ld_ctx,
+                                   const float* mask, int mask_mode, const float* lse, void* dqkv, long ld_dqkv, int B, int Sq,
+                                   int Sk, int nh, int head_size, const DropCfg& drop, const uint32_t* keep_bits,
+                                   hipStream_t stream);
+
 // ---- datapipe.hip: the data pipeline's token masking and region assembly
 int vt_mask_tokens_dispatch(const int64_t* ids, const uint8_t* special, const int64_t* token_classes, const float* u_mask,
                             const float* u_replace, const float* u_random, const int64_t* random_words, int64_t* out_ids,

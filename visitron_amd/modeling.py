@@ -372,13 +372,14 @@ def _centered_mask(mask_f32):   # (any dtype ops.center_mask takes; fp32 out)
     return ops.center_mask(mask_f32)   # (mask - mask.amax(1, keepdim) + 1 in fp32, from the caller's dtype, one launch)
 
 
-def _additive_mask_2d(attention_mask, B, S):
+def _additive_mask_2d(attention_mask, B, S, Sq=None):
     """The additive extended mask CaptionBertEncoder.forward receives: [B,1,1,S] (or [B,S]) -> contiguous fp32 [B,S];
-    [B,1,S,S] (the reference's 3-D attention_mask, encoder.py:226-229) -> contiguous fp32 [B,S,S]."""
+    [B,1,S,S] (the reference's 3-D attention_mask, encoder.py:226-229) -> contiguous fp32 [B,S,S].  Sq: the number of
+    queries where it is not S (history states: Sq new positions over S = Sh + Sq keys, [B,1,Sq,S] -> [B,Sq,S])."""
     m = attention_mask
     if m.dim() == 4 and m.shape[1] == 1 and m.shape[2] == 1:
         m = m[:, 0, 0, :]
-    elif m.dim() == 4 and m.shape[1] == 1 and m.shape[2] == S:
+    elif m.dim() == 4 and m.shape[1] == 1 and m.shape[2] == (S if Sq is None else Sq):
         m = m[:, 0]
         if m.shape[0] != B:
             m = m.expand(B, -1, -1)
@@ -400,7 +401,9 @@ def _attention_with_history(x_bf16, history_state, w_qkv, b_qkv, attention_mask,
     keys and values run over cat([history, hidden], 1) (:37-41) -- the packed projection is taken over the
     concatenated rows and the fused kernel over Sh + S positions, of which the last S query rows are the layer's
     context (the history rows' own queries are computed and dropped).  attention_mask: the additive extended mask over
-    the Sh + S keys (or pass mask_f32 [B, Sh+S] with its mask_additive flag).  -> (ctx bf16 [B*S, H], probs or None)."""
+    the Sh + S keys (or pass mask_f32 [B, Sh+S] with its mask_additive flag).  A per-query mask [B, S, Sh+S] together with
+    a history takes the rectangular kernel (ops.attention_rect_fwd: S queries over Sh + S keys).
+    -> (ctx bf16 [B*S, H], probs or None)."""
     H = nh * 64
     Sh = 0
     xs = x_bf16
@@ -411,9 +414,18 @@ def _attention_with_history(x_bf16, history_state, w_qkv, b_qkv, attention_mask,
     qkv = ops.linear(xs, w_qkv, b_qkv)
     mask = mask_f32
     if mask is None and attention_mask is not None:
-        mask = _additive_mask_2d(attention_mask, B, St)
+        mask = _additive_mask_2d(attention_mask, B, St, Sq=S)
     if mask is not None and mask.dim() == 3 and Sh:
-        raise NotImplementedError("per-query attention masks together with history states are not served")
+        lse = torch.empty((B, nh, S), dtype=torch.float32, device=x_bf16.device) if want_probs else None
+        ctx = ops.attention_rect_fwd(qkv, B, S, St, nh, mask=mask, mask_additive=True, head_scale=head_scale, lse=lse)
+        probs = None
+        if want_probs:   # the (square) probabilities kernel over the extended rows; the history rows' own queries are dropped
+            lse_ext = torch.zeros((B, nh, St), dtype=torch.float32, device=x_bf16.device)
+            lse_ext[:, :, Sh:] = lse
+            mask_ext = torch.cat([mask.new_zeros((B, Sh, St)), mask], 1).contiguous()
+            probs = ops.attention_probs(qkv, lse_ext, B, St, nh, mask=mask_ext, mask_additive=True,
+                                        head_scale=head_scale)[:, :, Sh:, :].contiguous()
+        return ctx, probs
     lse = torch.empty((B, nh, St), dtype=torch.float32, device=x_bf16.device) if want_probs else None
     ctx = ops.attention_fwd(qkv, B, St, nh, mask=mask, mask_additive=mask_additive, head_scale=head_scale, lse=lse)
     probs = None
@@ -938,7 +950,7 @@ class CaptionBertEncoder(nn.Module):
         """oscar/modeling_bert.py:140-169.  attention_mask is the ADDITIVE extended mask [B,1,1,S]."""
         B, S, H = hidden_states.shape
         Sh = 0 if encoder_history_states is None else encoder_history_states[0].shape[1]
-        mask = _additive_mask_2d(attention_mask, B, Sh + S) if attention_mask is not None else None
+        mask = _additive_mask_2d(attention_mask, B, Sh + S, Sq=S) if attention_mask is not None else None
         hs = _head_scale(head_mask, len(self.layer), self._heads, hidden_states.device)
         if _is_fp32(self):
             ops._require_hip(hidden_states)
@@ -1061,9 +1073,12 @@ class BertImgModelwithLocationEmbeds(BertPreTrainedModel):
                 else:
                     mask_f32 = _centered_mask(attention_mask.to(device=dev))
             elif attention_mask.dim() == 3:   # encoder.py:228-229 + :238-241: per-query mask -> additive bias [B,S,S]
-                if attention_mask.shape != (B, S, S):
+                if attention_mask.shape != (B, S, Sh + S):   # (with history states: the S new positions over Sh + S keys)
                     raise RuntimeError("3-D attention_mask shape %s does not match [%d, %d, %d]"
-                                       % (tuple(attention_mask.shape), B, S, S))
+                                       % (tuple(attention_mask.shape), B, S, Sh + S))
+                if Sh and _is_fp32(self):
+                    raise NotImplementedError("per-query attention masks together with history states are served by the "
+                                              "bf16 path")
                 mask_f32 = ((1.0 - attention_mask.to(device=dev, dtype=torch.float32)) * -10000.0).contiguous()
                 mask_is_additive = True
             else:
@@ -1187,9 +1202,6 @@ class BertImgModelwithLocationEmbeds(BertPreTrainedModel):
             # a caller that trains THROUGH the trunk (the rollout's OscarEncoder, agent.py:493-518): one autograd node
             # backed by the engine's forward / backward kernels.  Also train() under torch.no_grad() with dropout on
             # (agent.py:476-489, test(use_dropout=True)): the same forward with its dropout, no graph.
-            if encoder_history_states:
-                raise NotImplementedError("trunk-level training serves the forward without encoder_history_states "
-                                          "(output_hidden_states and output_attentions are served)")
             ops._require_hip(input_ids)
             from .training import autograd_trunk_forward
 
@@ -1200,8 +1212,9 @@ class BertImgModelwithLocationEmbeds(BertPreTrainedModel):
             if img_feats is not None:
                 batch.update(img_feats=img_feats, img_location_embeddings=img_location_embeddings)
             dt = next(self.parameters()).dtype
+            kw = dict(history=encoder_history_states) if encoder_history_states else {}   # (:271-274: text only, checked there)
             out = autograd_trunk_forward(self, batch, head_mask, want_hidden=self.encoder.output_hidden_states,
-                                         want_attn=self.encoder.output_attentions)
+                                         want_attn=self.encoder.output_attentions, **kw)
             res = (out[0].to(dt), out[1].to(dt))
             for extra in out[2:]:   # (sequence_output, pooled_output) + encoder_outputs[1:] = hidden states, then attentions (encoder.py:300-303)
                 res = res + (tuple(h.to(dt) for h in extra),)

@@ -640,6 +640,78 @@ def attention_fwd(qkv, B, S, nh, mask=None, mask_additive=False, head_scale=None
     return out
 
 
+def keep_words_rect(B, nh, Sq, Sk):
+    """Words of the rectangular attention's keep buffer (VT_KEEP_WORDS_RECT in include/visitron_hip.h): one per (batch, head,
+    32-query block, key), the key pitch Sk rounded up to 32.  Sq == Sk: keep_words(B, nh, Sk)."""
+    return B * nh * ((Sq + 31) // 32) * ((Sk + 31) // 32 * 32)
+
+
+def unpack_keep_bits_rect(keep_bits, B, nh, Sq, Sk):
+    """bool [B, nh, Sq, Sk] (query, key) from the keep words attention_rect_fwd wrote (word ((b nh + h) nqb + qb) kpitch + key,
+    bit j = query 32 qb + j, nqb = ceil(Sq / 32), kpitch = Sk rounded up to 32)."""
+    nqb = (Sq + 31) // 32
+    kp = (Sk + 31) // 32 * 32
+    w = keep_bits[:B * nh * nqb * kp].view(B, nh, nqb, 1, kp)
+    j = torch.arange(32, device=keep_bits.device, dtype=torch.int32).view(1, 1, 1, 32, 1)
+    bits = torch.bitwise_and(torch.bitwise_right_shift(w, j), 1)
+    return bits.reshape(B, nh, nqb * 32, kp)[:, :, :Sq, :Sk].bool()
+
+
+def _mask_mode_rect(mask, mask_additive, B, Sq, Sk):
+    """_mask_mode over Sk keys: 0 raw [B,Sk], 1 additive [B,Sk], 2 additive per query [B,Sq,Sk]."""
+    if mask is None:
+        return 0
+    assert mask.dtype == torch.float32 and mask.is_contiguous()
+    if mask.dim() == 3:
+        assert mask_additive and mask.shape == (B, Sq, Sk), "per-query masks are passed as the additive bias [B,Sq,Sk]"
+        return 2
+    assert mask.numel() == B * Sk
+    return 1 if mask_additive else 0
+
+
+def attention_rect_fwd(qkv, B, Sq, Sk, nh, mask=None, mask_additive=False, head_scale=None, out=None, lse=None, drop=NO_DROP,
+                       keep_bits=None):
+    """Sq queries over Sk >= Sq keys (encoder_history_states): qkv [B*Sk, 3*nh*64] bf16 of the extended rows, a sequence's
+    queries its last Sq rows; mask fp32 over the Sk keys -> context [B*Sq, nh*64] bf16.  lse: fp32 [B, nh, Sq] or None.
+    keep_bits (int32 [keep_words_rect(B, nh, Sq, Sk)], dropout on): receives the keep decisions for attention_rect_bwd."""
+    _require_hip(qkv, mask, head_scale, out, lse, keep_bits)
+    assert qkv.dtype == BF16 and qkv.shape[0] >= B * Sk
+    if keep_bits is not None:
+        assert keep_bits.dtype == torch.int32 and keep_bits.is_contiguous() and keep_bits.numel() >= keep_words_rect(B, nh, Sq, Sk)
+    if lse is not None:
+        assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() >= B * nh * Sq
+    H = nh * 64
+    if out is None:
+        out = torch.empty((B * max(Sq, 0), H), dtype=BF16, device=qkv.device)
+    mode = _mask_mode_rect(mask, mask_additive, B, Sq, Sk) if 1 <= Sq <= Sk else 0
+    with _timed("attention_rect_fwd_d64", 4.0 * B * nh * Sq * Sk * 64, 2.0 * B * (3 * Sk + Sq) * H):
+        rc = _lib.load().vt_attention_rect_fwd_bf16(
+            _ptr(qkv), qkv.stride(0), _ptr(mask), mode, _ptr(head_scale), _ptr(out), out.stride(0), _ptr(lse), B, Sq, Sk, nh, 64,
+            float(drop[0]), int(drop[1]), int(drop[2]), _ptr(keep_bits), _stream())
+    _lib.check(rc, "vt_attention_rect_fwd_bf16")
+    return out
+
+
+def attention_rect_bwd(qkv, dctx, ctx, lse, B, Sq, Sk, nh, mask=None, mask_additive=False, out=None, drop=NO_DROP,
+                       keep_bits=None):
+    """Gradient of attention_rect_fwd w.r.t. the packed qkv: dqkv [B*Sk, 3*nh*64] bf16; the dq columns of the Sk - Sq history
+    rows of every sequence are written as zeros.  No workspace, no atomics: the same bits on every run."""
+    _require_hip(qkv, dctx, ctx, lse, mask, out, keep_bits)
+    assert qkv.dtype == BF16 and dctx.dtype == BF16 and ctx.dtype == BF16 and lse.dtype == torch.float32
+    if keep_bits is not None:
+        assert keep_bits.dtype == torch.int32 and keep_bits.is_contiguous() and keep_bits.numel() >= keep_words_rect(B, nh, Sq, Sk)
+    H = nh * 64
+    if out is None:
+        out = torch.empty((B * Sk, 3 * H), dtype=BF16, device=qkv.device)
+    mode = _mask_mode_rect(mask, mask_additive, B, Sq, Sk) if 1 <= Sq <= Sk else 0
+    with _timed("attention_rect_bwd_d64", 14.0 * B * nh * Sq * Sk * 64, 2.0 * B * (6 * Sk + 2 * Sq) * H):
+        rc = _lib.load().vt_attention_rect_bwd_bf16(
+            _ptr(qkv), qkv.stride(0), _ptr(dctx), dctx.stride(0), _ptr(ctx), ctx.stride(0), _ptr(mask), mode, _ptr(lse),
+            _ptr(out), out.stride(0), B, Sq, Sk, nh, 64, float(drop[0]), int(drop[1]), int(drop[2]), _ptr(keep_bits), _stream())
+    _lib.check(rc, "vt_attention_rect_bwd_bf16")
+    return out
+
+
 def attention_probs(qkv, lse, B, S, nh, mask=None, mask_additive=False, head_scale=None):
     """fp32 [B, nh, S, S] attention probabilities (config.output_attentions) from qkv and attention_fwd's lse."""
     _require_hip(qkv, lse, mask, head_scale)

@@ -195,6 +195,24 @@ def _ctx_raw(self, layer):
 _TrainBuffers.ctx_raw = _ctx_raw
 
 
+def _history_state(history, B, H, L, dev):
+    """encoder_history_states as the unrolled layer sequences carry them: the bf16 rows each layer prepends ("src"), which
+    tensors want a gradient ("need"), and per layer what the forward keeps for the backward -- the extended rows "xs"
+    [B*St, H], their projection "qkv" [B*St, 3H], the rectangular attention's keep words -- and what the backward leaves,
+    "d": fp32 [B, Sh, H] per layer, None where the history tensor does not require grad."""
+    history = list(history)
+    if len(history) != L:
+        raise RuntimeError("encoder_history_states must hold one tensor per layer (%d), got %d" % (L, len(history)))
+    Sh = history[0].shape[1]
+    for h in history:
+        ops._require_hip(h)
+        if tuple(h.shape) != (B, Sh, H):
+            raise RuntimeError("every encoder_history_states tensor must be [batch, Sh, hidden] = [%d, %d, %d], got %s"
+                               % (B, Sh, H, tuple(h.shape)))
+    return dict(Sh=Sh, src=[h.detach().to(device=dev, dtype=BF16).contiguous() for h in history],
+                need=[bool(h.requires_grad) for h in history], xs=[None] * L, qkv=[None] * L, keep=[None] * L, d=[None] * L)
+
+
 class _TrunkOnly(torch.nn.Module):
     """A bare BertImgModelwithLocationEmbeds presented to the engine under the parameter names it has inside a
     PreTrainOscar ("bert." + name): train.py:47 hands `model.bert` to the rollout agent, which trains through it."""
@@ -476,10 +494,12 @@ class PretrainEngine(object):
         return max(0.0, float(self.t_total - s) / float(max(1.0, self.t_total - self.warmup_steps)))
 
     # ------------------------------------------------------------------------------ forward + backward
-    def _trunk_fwd(self, batch, head_mask, labels, token_labels, training, allow_compact, comm=None):
+    def _trunk_fwd(self, batch, head_mask, labels, token_labels, training, allow_compact, comm=None, history=None):
         """The trunk's forward (embeddings, region projection, encoder layers, pooler) with every activation the backward
         needs kept in the (B, S) buffer set; returns the step's state (a namespace of the locals below).  labels /
-        token_labels (optional): the supervised rows are located here, where the host synchronises anyway."""
+        token_labels (optional): the supervised rows are located here, where the host synchronises anyway.
+        history (optional): encoder_history_states, one [B, Sh, H] tensor per layer -- layer l's keys and values run over
+        cat([history[l], hidden], 1) (oscar/modeling_bert.py:37-41, 148-155) and the mask covers those Sh + S keys."""
         m, cfg, f = self.model, self.cfg, self.flat
         self._require_ownership()
         f.reattach_grads()
@@ -490,16 +510,27 @@ class PretrainEngine(object):
         R = 0 if img is None else img.shape[1]
         S, H, I, nh, L = T + R, cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.num_hidden_layers
         M = B * S
+        hist = None
+        if history:
+            assert img is None, "Cannot take image features while using encoder history states"   # encoder.py:271-274
+            if allow_compact:
+                raise NotImplementedError("encoder_history_states together with row compaction (unmasked_only) is not served")
+            if comm is not None:
+                raise NotImplementedError("encoder_history_states together with the chunked data-parallel backward is not served")
+            hist = _history_state(history, B, H, L, dev)
+        St = S + (0 if hist is None else hist["Sh"])
         am = batch.get("attention_mask")
         mask = None if am is None else am.to(torch.float32).contiguous()
         mask_additive = False
         if mask is not None and mask.dim() == 3:   # per-query mask -> additive bias [B, S, S] (encoder.py:228-229, :238-241)
-            if mask.shape != (B, S, S):
-                raise RuntimeError("3-D attention_mask must be [batch, text+region, text+region]")
+            if mask.shape != (B, S, St):
+                raise RuntimeError("3-D attention_mask must be [batch, text+region, text+region]" if hist is None else
+                                   "3-D attention_mask must be [batch, text, history+text]")
             mask = ((1.0 - mask) * -10000.0).contiguous()
             mask_additive = True
-        elif mask is not None and mask.shape != (B, S):
-            raise RuntimeError("attention_mask must be [batch, text+region]")
+        elif mask is not None and mask.shape != (B, St):
+            raise RuntimeError("attention_mask must be [batch, text+region]" if hist is None else
+                               "attention_mask must be [batch, history+text]")
         from .modeling import _centered_mask, _head_scale
         if mask is not None and not mask_additive:
             mask = _centered_mask(mask)   # one constant per sequence off the additive bias: same softmax, well-scaled numbers
@@ -617,7 +648,9 @@ class PretrainEngine(object):
         if lay is not None:
             x_enc, enc_mask = bufs.x0c[:Mr], None
             torch.index_select(x0, 0, lay.index, out=x_enc)
-        if ops.profiling() or hs is not None:
+        if hist is not None:
+            self._encoder_forward_unrolled(bufs, x_enc, enc_mask, B, S, p_h, p_a, seed, lay, mask_additive, hs, hist=hist)
+        elif ops.profiling() or hs is not None:
             self._encoder_forward_unrolled(bufs, x_enc, enc_mask, B, S, p_h, p_a, seed, lay, mask_additive, hs)
         else:
             ops.encoder_forward(self.w_tab, bufs.acts, x_enc, enc_mask, mask_additive, None, B, S, H, nh, I,
@@ -817,7 +850,12 @@ class PretrainEngine(object):
         bufs.fit_dq32()   # (the deterministic switch is read here, per backward: no copy of it is kept)
         if d_hidden is not None and comm is not None:
             raise NotImplementedError("gradients of intermediate hidden states together with the chunked data-parallel backward")
-        if ops.profiling() or hs is not None:
+        if st.hist is not None:
+            if comm is not None:
+                raise NotImplementedError("encoder_history_states together with the chunked data-parallel backward is not served")
+            self._encoder_backward_unrolled(bufs, x_enc, enc_mask, g, B, S, acc, p_h, p_a, seed, lay, mask_additive, hs,
+                                            inject=d_hidden, hist=st.hist)
+        elif ops.profiling() or hs is not None:
             self._encoder_backward_unrolled(bufs, x_enc, enc_mask, g, B, S, acc, p_h, p_a, seed, lay, mask_additive, hs,
                                             inject=d_hidden)
         elif d_hidden is not None:
@@ -913,21 +951,30 @@ class PretrainEngine(object):
                 gi.copy_(self.dw_img[:, :D]); gl.copy_(self.dw_img[:, D:D + 128]); gbi.copy_(self.db_img); gbl.copy_(self.db_img)
 
     # ------------------------------------------------------------------------------ trunk-level training
-    def trunk_forward(self, batch, head_mask=None, training=None, unmasked_only=False, want_hidden=False, want_attn=False):
+    def trunk_forward(self, batch, head_mask=None, training=None, unmasked_only=False, want_hidden=False, want_attn=False,
+                      history=None):
         """BertImgModelwithLocationEmbeds.forward for a caller that back-propagates through it (the rollout's
         OscarEncoder, agent.py:493-518): -> (sequence_output fp32 [B,S,H], pooled_output fp32 [B,H], state).
         unmasked_only: the caller vouches that it reads sequence_output only at positions whose attention mask is not
         zero (OscarEncoder: pack_padded_sequence drops the rest); the step may then run on those rows alone (the row
-        compaction of forward_backward) and the other positions of sequence_output are zero."""
+        compaction of forward_backward) and the other positions of sequence_output are zero.
+        history: encoder_history_states, one [B, Sh, H] tensor per layer (text-only batches; the attention mask covers the
+        Sh + S keys, [B, Sh+S] or per query [B, S, Sh+S]); trunk_backward then leaves their gradients in st.d_history."""
         if training is None:
             training = self.model.bert.training
         if self.precision == "fp32":
+            if history:
+                raise NotImplementedError("PretrainEngine(precision='fp32') does not serve encoder_history_states")
             if unmasked_only or want_hidden or want_attn:
                 raise NotImplementedError("PretrainEngine(precision='fp32') serves trunk_forward without unmasked_only, "
                                           "want_hidden and want_attn")
             st = training_f32.trunk_forward(self, batch, head_mask, bool(training))
             return st.seq.view(st.B, st.S, st.H).clone(), st.pooled.clone(), st
-        st = self._trunk_fwd(batch, head_mask, None, None, bool(training), bool(unmasked_only))
+        if history:
+            st = self._trunk_fwd(batch, head_mask, None, None, bool(training), bool(unmasked_only), history=history)
+        else:
+            st = self._trunk_fwd(batch, head_mask, None, None, bool(training), bool(unmasked_only))
+        st.d_history = None
         # the caller's hidden states come from the fp16 copy of the last LayerNorm's output where the layer keeps one (the
         # bf16 copy is the heads' / pooler's GEMM operand)
         n = st.seq.shape[0]
@@ -962,6 +1009,9 @@ class PretrainEngine(object):
             nh_, pa = st.nh, st.p_a
             attn = []
             for l, d in enumerate(st.bufs.layers):
+                if st.hist is not None:
+                    attn.append(self._history_probs(st, l, d))
+                    continue
                 pr = ops.attention_probs(d["qkv"][:n], d["lse"], st.B, st.S, nh_, mask=st.enc_mask, mask_additive=st.mask_additive,
                                          head_scale=None if st.hs is None else st.hs[l].contiguous())
                 if pa > 0.0:
@@ -986,10 +1036,29 @@ class PretrainEngine(object):
         hidden.append(seq.clone())
         return (seq, st.pooled.clone(), st, hidden) + ((attn,) if want_attn else ())
 
+    def _history_probs(self, st, l, d):
+        """all_attentions of layer l of a forward with history states: fp32 [B, heads, S, Sh+S], after dropout and head_mask.
+        The probabilities kernel is square: it runs over the extended projection with the saved log-sum-exp in the query
+        rows (the history rows' own queries get 0 and are dropped, as the inference path drops them)."""
+        B, S, nh, Sh = st.B, st.S, st.nh, st.hist["Sh"]
+        St = Sh + S
+        lse = torch.zeros((B, nh, St), dtype=torch.float32, device=st.dev)
+        lse[:, :, Sh:] = d["lse"]
+        mask = st.enc_mask
+        if mask is not None and mask.dim() == 3:
+            mask = torch.cat([mask.new_zeros((B, Sh, St)), mask], 1).contiguous()
+        pr = ops.attention_probs(st.hist["qkv"][l], lse, B, St, nh, mask=mask, mask_additive=st.mask_additive,
+                                 head_scale=None if st.hs is None else st.hs[l].contiguous())[:, :, Sh:, :].contiguous()
+        if st.p_a > 0.0:
+            keep = ops.unpack_keep_bits_rect(st.hist["keep"][l], B, nh, S, St)
+            pr = pr * keep / (1.0 - ops.attn_drop_p(st.p_a))
+        return pr
+
     def trunk_backward(self, st, d_seq, d_pooled=None, accumulate=False, d_hidden=None):
         """Gradients of the trunk's parameters into the flat slab, given dL/d(sequence_output) [B,S,H] and / or
         dL/d(pooled_output) [B,H] (either may be None).  The pooler's gradients are zeroed when d_pooled is None, the
-        region projection's when the forward had no regions."""
+        region projection's when the forward had no regions.  After a forward with history states, st.d_history holds
+        dL/d(history[l]) as fp32 [B, Sh, H] per layer (None for a tensor that does not require grad)."""
         if self.precision == "fp32":
             if d_hidden is not None:
                 raise NotImplementedError("PretrainEngine(precision='fp32') serves trunk_backward without d_hidden")
@@ -1022,6 +1091,8 @@ class PretrainEngine(object):
             self._grad(pw).zero_()
             self._grad(pb).zero_()
         self._trunk_bwd(st, g32, acc, d_hidden=extra)
+        if st.hist is not None:
+            st.d_history = list(st.hist["d"])
         if st.img is None and not acc:
             for prm in (m.bert.img_embedding.weight, m.bert.img_embedding.bias, m.bert.location_embeds.weight,
                         m.bert.location_embeds.bias):
@@ -1043,7 +1114,10 @@ class PretrainEngine(object):
 
     # ---- the launch sequences of vt_encoder_forward/backward_bf16 issued op by op (bench.py's per-kernel timing)
     def _encoder_forward_unrolled(self, bufs, x0, mask, B, S, p_h=0.0, p_a=0.0, seed=0, lay=None, mask_additive=False,
-                                  hs=None):
+                                  hs=None, hist=None):
+        """hist (_history_state): layer l projects cat([history[l], layer input], 1) and attends with its S queries over
+        those St = Sh + S keys (ops.attention_rect_fwd); the extended rows and their projection are kept in hist for the
+        backward.  The rest of the layer is the same."""
         cfg = self.cfg
         nh, eps = cfg.num_attention_heads, cfg.layer_norm_eps
         cur, cur_h, cur_ln = x0, None, None
@@ -1051,8 +1125,21 @@ class PretrainEngine(object):
         for l, ((t, _), a) in enumerate(zip(self._keep, bufs.layers)):
             a = {k: (v if k in ("lse", "keep_bits") else v[:n]) for k, v in a.items()}   # the rows in use (all, or the compacted ones)
             kb = a.get("keep_bits") if p_a > 0.0 else None
-            ops.linear(cur, t["w_qkv"], t["b_qkv"], out=a["qkv"])
-            if hs is None:
+            if hist is None:
+                ops.linear(cur, t["w_qkv"], t["b_qkv"], out=a["qkv"])
+            if hist is not None:
+                St, H = hist["Sh"] + S, cur.shape[1]
+                xs = torch.cat([hist["src"][l], cur.view(B, S, H)], 1).reshape(B * St, H)
+                qkv = ops.linear(xs, t["w_qkv"], t["b_qkv"])
+                kbr = torch.empty(ops.keep_words_rect(B, nh, S, St), dtype=torch.int32, device=cur.device) if p_a > 0.0 else None
+                hist["xs"][l], hist["qkv"][l], hist["keep"][l] = xs, qkv, kbr
+                # (head_mask: the kernel's own context is kept for the backward, its scaled copy feeds the output projection)
+                raw = a["ctx"] if hs is None else bufs.ctx_raw(l)[:n]
+                ops.attention_rect_fwd(qkv, B, S, St, nh, mask=mask, mask_additive=mask_additive, out=raw, lse=a["lse"],
+                                       drop=(p_a, seed, ops.site_attn(l)), keep_bits=kbr)
+                if hs is not None:
+                    ops.scale_heads(raw, hs[l].contiguous(), out=a["ctx"])
+            elif hs is None:
                 ops.attention_fwd(a["qkv"], B, S, nh, mask=mask, mask_additive=mask_additive, out=a["ctx"], lse=a["lse"],
                                   drop=(p_a, seed, ops.site_attn(l)), seq=lay, keep_bits=kb)
             else:
@@ -1094,7 +1181,12 @@ class PretrainEngine(object):
         return dict(ws_b=bufs.ws_b, side_stream=self._side_stream)
 
     def _encoder_backward_unrolled(self, bufs, x0, mask, g, B, S, acc, p_h=0.0, p_a=0.0, seed=0, lay=None,
-                                   mask_additive=False, hs=None, inject=None):
+                                   mask_additive=False, hs=None, inject=None, hist=None):
+        """hist (_history_state of the forward): the rectangular attention backward gives the gradient of the extended
+        projection [B*St, 3H]; one dgrad GEMM over those rows yields the hidden rows' gradient (joined with the residual
+        gradient) and, in fp32, d_history[l] (kept in hist["d"] for history tensors that require grad); the packed QKV
+        weight gradient is a launch of its own over the B*St rows (the dq columns of history rows are zero, so the query
+        weights see the hidden rows only; key and value biases apply to history rows as in the reference)."""
         cfg = self.cfg
         nh, eps, M = cfg.num_attention_heads, cfg.layer_norm_eps, x0.shape[0]
         rowed = ("g_pre", "g_pre2", "g_mid", "g_ctx", "g_qkv", "g_pre_d", "g_pre2_d")
@@ -1120,6 +1212,21 @@ class PretrainEngine(object):
             if hs is not None:   # back through the head scaling: dL/d(raw context) = head_mask * dL/d(scaled context)
                 g_ctx = ops.scale_heads(w["g_ctx"], hs[l].contiguous())
                 ctx_l = bufs.ctx_raw(l)[:M]
+            if hist is not None:
+                Sh, H = hist["Sh"], g.shape[1]
+                St = Sh + S
+                g_ext = ops.attention_rect_bwd(hist["qkv"][l], g_ctx, ctx_l, a["lse"], B, S, St, nh, mask=mask,
+                                               mask_additive=mask_additive, drop=(p_a, seed, ops.site_attn(l)),
+                                               keep_bits=hist["keep"][l] if p_a > 0.0 else None)
+                gx = ops.linear(g_ext, wt["wt_qkv"], out_f32=True).view(B, St, H)
+                g.copy_((gx[:, Sh:] + w["g_pre2"].view(B, S, H).float()).reshape(M, H))
+                if hist["need"][l]:
+                    hist["d"][l] = gx[:, :Sh].clone()
+                ops.wgrad([dict(dy=g_ext, x=hist["xs"][l], dw=gr["d_w_qkv"], db=gr["d_b_qkv"], accumulate=acc)], B * St)
+                ops.wgrad([dict(dy=w["g_mid"], x=a["attn_out"], dw=gr["d_w_in"], db=gr["d_b_in"], accumulate=acc),
+                           dict(dy=g_pre_dn, x=a["mid"], dw=gr["d_w_out"], db=gr["d_b_out"], accumulate=acc),
+                           dict(dy=g_pre2_dn, x=a["ctx"], dw=gr["d_w_ao"], db=gr["d_b_ao"], accumulate=acc)], M)
+                continue
             ops.attention_bwd(a["qkv"], g_ctx, ctx_l, a["lse"], B, S, nh, mask=mask, mask_additive=mask_additive,
                               out=w["g_qkv"], delta_ws=w["delta"], dq32_ws=w.get("dq32"), drop=(p_a, seed, ops.site_attn(l)),
                               seq=lay, keep_bits=a.get("keep_bits") if p_a > 0.0 else None)
@@ -1591,10 +1698,17 @@ class _TrunkWithGrads(torch.autograd.Function):
     parameter gradients to autograd."""
 
     @staticmethod
-    def forward(ctx, engine, batch, head_mask, unmasked_only, want_hidden, want_attn, *params):
-        out = engine.trunk_forward(batch, head_mask, unmasked_only=unmasked_only, want_hidden=want_hidden, want_attn=want_attn)
+    def forward(ctx, engine, batch, head_mask, unmasked_only, want_hidden, want_attn, n_history, *tensors):
+        # tensors: the n_history encoder_history_states (inputs with gradients of their own), then the parameters
+        history, params = tensors[:n_history], tensors[n_history:]
+        if n_history:
+            out = engine.trunk_forward(batch, head_mask, unmasked_only=unmasked_only, want_hidden=want_hidden,
+                                       want_attn=want_attn, history=history)
+        else:
+            out = engine.trunk_forward(batch, head_mask, unmasked_only=unmasked_only, want_hidden=want_hidden, want_attn=want_attn)
         seq, pooled, st = out[:3]
         ctx.engine, ctx.st = engine, st
+        ctx.history_like = [(h.dtype, h.device) for h in history]
         ctx.names = [engine._name_of(p) for p in params]
         ctx.n_hidden = len(out[3]) if want_hidden else 0
         ctx.set_materialize_grads(False)
@@ -1614,7 +1728,9 @@ class _TrunkWithGrads(torch.autograd.Function):
         if d_pooled is None:
             unused.add("bert.pooler.")
         grads = [None if n.startswith(tuple(unused)) else f.view(f.g, n).clone() for n in ctx.names]
-        return (None, None, None, None, None, None) + tuple(grads)
+        d_history = tuple(None if d is None else d.to(device=dev, dtype=dt)
+                          for d, (dt, dev) in zip(st.d_history or (), ctx.history_like))
+        return (None, None, None, None, None, None, None) + d_history + tuple(grads)
 
 
 class _TrunkLazyGrads(torch.autograd.Function):
@@ -1650,18 +1766,23 @@ def lazy_autograd_trunk(trunk, batch, head_mask, seq, pooled):
     return _TrunkLazyGrads.apply(trunk, batch, head_mask, seq, pooled, *params)
 
 
-def autograd_trunk_forward(trunk, batch, head_mask=None, unmasked_only=False, want_hidden=False, want_attn=False):
+def autograd_trunk_forward(trunk, batch, head_mask=None, unmasked_only=False, want_hidden=False, want_attn=False, history=None):
     """BertImgModelwithLocationEmbeds.forward in training mode: (sequence_output, pooled_output) that back-propagate into the
     trunk's parameters through the HIP backward; under torch.no_grad() the same forward (dropout included) without a graph.
     unmasked_only: see PretrainEngine.trunk_forward.  want_hidden: one more element, the tuple of all_hidden_states
     (embedding output + every layer's output, oscar/modeling_bert.py:146-158), each differentiable like sequence_output.
-    want_attn: one more, the tuple of all_attentions (per layer, after dropout and head_mask) -- values only."""
+    want_attn: one more, the tuple of all_attentions (per layer, after dropout and head_mask) -- values only.
+    history: encoder_history_states (one [B, Sh, H] tensor per layer); the tensors among them that require grad receive
+    their gradients like the parameters do."""
     eng = _bridge_engine(trunk)
+    history = list(history) if history else []
     if not torch.is_grad_enabled():
-        out = eng.trunk_forward(batch, head_mask, unmasked_only=unmasked_only, want_hidden=want_hidden, want_attn=want_attn)
+        kw = dict(history=history) if history else {}
+        out = eng.trunk_forward(batch, head_mask, unmasked_only=unmasked_only, want_hidden=want_hidden, want_attn=want_attn, **kw)
         return (out[0], out[1]) + ((tuple(out[3]),) if want_hidden else ()) + ((tuple(out[4]),) if want_attn else ())
     params = [p for p in trunk.parameters() if p.requires_grad]
-    out = _TrunkWithGrads.apply(eng, batch, head_mask, bool(unmasked_only), bool(want_hidden), bool(want_attn), *params)
+    out = _TrunkWithGrads.apply(eng, batch, head_mask, bool(unmasked_only), bool(want_hidden), bool(want_attn), len(history),
+                                *history, *params)
     L1 = trunk.config.num_hidden_layers + 1
     res = (out[0], out[1])
     k = 2
