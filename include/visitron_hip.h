@@ -541,6 +541,41 @@ int vt_softdot_attention_bwd_split_f32(const float* target, const float* context
                                        const uint8_t* mask, const float* d_weighted, const float* d_attn, float* d_context,
                                        float* ws, int B, int L, int D, int output_prob, vt_stream_t stream);
 
+/* ---- the turn-based task's decoder step (ABI 19): tasks/turn_based/agent_models.py:277-319, agent.py:307-338 ------------------
+ *
+ * nn.Embedding + torch.cat + nn.LSTMCell (agent_models.py:309-315) in one launch:
+ *   gates = [emb | feature] . w_ih^T + h_prev . w_hh^T + bias, c_out = sig(f) c_prev + sig(i) tanh(g), h_out = sig(o) tanh(c_out)
+ * (gate order i, f, g, o).  The first operand comes in one of two forms: ids int64 [B] with table fp32 [A, E] (row stride
+ * ld_t; x_emb NULL), or a ready fp32 block x_emb [B, E] (row stride ld_e; ids and table NULL) -- the training forward, where
+ * dropout has been applied already.  feature fp32 [B, F] (row stride ld_f).  Any E, F >= 1 and any 4-byte-aligned rows:
+ * loads wider than 4 bytes happen only at addresses aligned for them and never leave a row.  w_ih bf16 [4*hs, Kpad] (row
+ * stride ldw, a multiple of 8; zero past E + F; Kpad a multiple of 32), w_hh bf16 [4*hs, hs], bias fp32 [4*hs] = b_ih + b_hh,
+ * hs a multiple of 128; h_prev / c_prev / h_out / c_out fp32 [B, hs] contiguous; h_out must not alias h_prev
+ * (VT_ERR_UNSUPPORTED), c_out may be c_prev.  An id outside [0, A): that row's embedding counts as zero and *err_flag
+ * (optional) is set to 1.  sv_gates fp32 [B, 4*hs], sv_c fp32 [B, hs], sv_h bf16 [B, hs] (each optional) receive what
+ * vt_lstm_step_bwd_f32 reads. */
+int vt_turn_lstm_cell_f32(const int64_t* ids, const float* table, int64_t ld_t, int A, const float* x_emb, int64_t ld_e, int E,
+                          const float* feature, int64_t ld_f, int F, const float* h_prev, const float* c_prev, const void* w_ih,
+                          int64_t ldw, int Kpad, const void* w_hh, const float* bias, float* h_out, float* c_out,
+                          float* sv_gates, float* sv_c, void* sv_h, int32_t* err_flag, int B, int hs, vt_stream_t stream);
+
+/* The action head around that step (agent.py:316-338) in one launch.  logit fp32 [B, A] (row stride ld, 1 <= A <= 64; not
+ * modified); blocked uint8 [B, A] (row stride ld_blk; optional): non-zero = the logit counts as -inf.  loss[0] = mean over
+ * the rows with target != ignore_index of logsumexp - logit[target] (+inf for a blocked target, NaN without a counted
+ * row), count[0] = the number of those rows.  a_t int64 [B]: mode 0 = target, 1 = lowest index of the row maximum, 2 = the
+ * smallest a with sum_{j<=a} e_j > u sum_j e_j, e_j = exp(l_j - max), u = (hash32(seed, row) >> 8) * 2^-24 (never a blocked
+ * entry; the last unblocked one if rounding leaves none).  A target outside [0, A) other than ignore_index is left out of
+ * the loss and sets *err_flag (optional). */
+int vt_turn_action_head_f32(const float* logit, int64_t ld, const int64_t* target, const uint8_t* blocked, int64_t ld_blk,
+                            int64_t ignore_index, int B, int A, int mode, uint32_t seed, float* loss, float* count,
+                            int64_t* a_t, int32_t* err_flag, vt_stream_t stream);
+
+/* Its gradient: dlogit [B, A] (row stride ld_d) = g[0] (softmax - onehot(target)) / count[0] on the counted rows, 0 on the
+ * other rows and on blocked entries; g and count are device scalars (count as vt_turn_action_head_f32 left it). */
+int vt_turn_action_head_bwd_f32(const float* logit, int64_t ld, const int64_t* target, const uint8_t* blocked, int64_t ld_blk,
+                                int64_t ignore_index, int B, int A, const float* g, const float* count, float* dlogit,
+                                int64_t ld_d, vt_stream_t stream);
+
 /* out[c, r] = in[r, c] (bf16; R, C multiples of 8): refreshes the transposed weight copies (W^T of every nn.Linear on the
  * path, oscar/modeling_bert.py:43-45,94,119,120) that the
  * dgrad GEMMs consume (vt_layer_weights_t). */

@@ -21,7 +21,7 @@ const char* vt_error_string(int code) {
   }
 }
 
-int vt_abi_version(void) { return 18; }
+int vt_abi_version(void) { return 19; }
 
 // deterministic training mode (common.hpp): one word for the process, read by every dispatch at launch time
 void vt_set_deterministic(int on) { vt_deterministic_word().store(on ? 1 : 0, std::memory_order_relaxed); }
@@ -370,6 +370,37 @@ int vt_softdot_attention_f32(const float* target, const float* context, int64_t 
   a.target = target; a.context = context; a.ld_batch = ld_batch; a.ld_row = ld_row; a.mask = mask;
   a.weighted = weighted; a.attn = attn; a.B = B; a.L = L; a.D = D; a.output_prob = output_prob;
   return vt_softdot_dispatch(a, (hipStream_t)stream);
+}
+
+int vt_turn_lstm_cell_f32(const int64_t* ids, const float* table, int64_t ld_t, int A, const float* x_emb, int64_t ld_e, int E,
+                          const float* feature, int64_t ld_f, int F, const float* h_prev, const float* c_prev, const void* w_ih,
+                          int64_t ldw, int Kpad, const void* w_hh, const float* bias, float* h_out, float* c_out,
+                          float* sv_gates, float* sv_c, void* sv_h, int32_t* err_flag, int B, int hs, vt_stream_t stream) {
+  TbCellArgs a;
+  a.ids = (const long*)ids; a.table = table; a.ld_t = ld_t; a.A = A; a.x_emb = x_emb; a.ld_e = ld_e; a.feature = feature;
+  a.ld_f = ld_f; a.E = E; a.F = F; a.h_prev = h_prev; a.c_prev = c_prev; a.w_ih = (const bf16_t*)w_ih; a.ldw = ldw;
+  a.Kpad = Kpad; a.w_hh = (const bf16_t*)w_hh; a.bias = bias; a.h_out = h_out; a.c_out = c_out; a.sv_gates = sv_gates;
+  a.sv_c = sv_c; a.sv_h = (bf16_t*)sv_h; a.err = (int*)err_flag; a.B = B; a.hs = hs;
+  return vt_tb_lstm_cell_dispatch(a, (hipStream_t)stream);
+}
+
+int vt_turn_action_head_f32(const float* logit, int64_t ld, const int64_t* target, const uint8_t* blocked, int64_t ld_blk,
+                            int64_t ignore_index, int B, int A, int mode, uint32_t seed, float* loss, float* count,
+                            int64_t* a_t, int32_t* err_flag, vt_stream_t stream) {
+  TbHeadArgs a;
+  a.logit = logit; a.ld = ld; a.target = (const long*)target; a.blocked = blocked; a.ld_blk = ld_blk;
+  a.ignore_index = ignore_index; a.B = B; a.A = A; a.mode = mode; a.seed = seed; a.loss = loss; a.count = count;
+  a.a_t = (long*)a_t; a.err = (int*)err_flag;
+  return vt_tb_action_head_dispatch(a, (hipStream_t)stream);
+}
+
+int vt_turn_action_head_bwd_f32(const float* logit, int64_t ld, const int64_t* target, const uint8_t* blocked, int64_t ld_blk,
+                                int64_t ignore_index, int B, int A, const float* g, const float* count, float* dlogit,
+                                int64_t ld_d, vt_stream_t stream) {
+  TbHeadBwdArgs a;
+  a.logit = logit; a.ld = ld; a.target = (const long*)target; a.blocked = blocked; a.ld_blk = ld_blk;
+  a.ignore_index = ignore_index; a.B = B; a.A = A; a.g = g; a.count = count; a.dlogit = dlogit; a.ld_d = ld_d;
+  return vt_tb_action_head_bwd_dispatch(a, (hipStream_t)stream);
 }
 
 int vt_transpose_bf16(const void* in, int64_t ldi, void* out, int64_t ldo, int R, int C, vt_stream_t stream) {

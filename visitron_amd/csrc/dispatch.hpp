@@ -192,6 +192,11 @@ int vt_lstm_sequence_bwd_dispatch(const float* d_seq_out, long ldd_b, long ldd_t
                                   const void* w_hh_t, const int* lengths, const float* sv_gates, const float* sv_c, void* dgates,
                                   long S_sv, int B, int hs, int T, int reverse, hipStream_t stream);
 
+// ---- turn_based.hip
+int vt_tb_lstm_cell_dispatch(const TbCellArgs& a, hipStream_t stream);
+int vt_tb_action_head_dispatch(const TbHeadArgs& a, hipStream_t stream);
+int vt_tb_action_head_bwd_dispatch(const TbHeadBwdArgs& a, hipStream_t stream);
+
 // ---- rowops.hip: LayerNorm, embeddings, losses, optimizer and the other row kernels
 int vt_layernorm_dispatch(const void* x, long ldx, void* y, long ldy, const float* gamma, const float* beta,
                           float* mean, float* rstd, int M, int H, float eps, int grp_rows, int grp_stride,

@@ -77,3 +77,44 @@ struct LstmPersistArgs {
   unsigned* sync;                          // [0] arrival counter, [1] timeout flag (zeroed by the launcher)
   int B, hs, T, reverse;
 };
+
+// The turn-based decoder's LSTM cell fused with its input projection (turn_based.hip).
+struct TbCellArgs {
+  const long* ids; const float* table; long ld_t; int A;   // first operand, form 1: embedding rows table[ids[b]] ([A, E] fp32)
+  const float* x_emb; long ld_e;                           // form 2: a ready fp32 [B, E] block (ids == null)
+  const float* feature; long ld_f;                         // [B, F] fp32
+  int E, F;
+  const float* h_prev;               // [B, hs] fp32, 16-byte aligned
+  const float* c_prev;               // [B, hs] fp32 (may be c_out)
+  const bf16_t* w_ih; long ldw;      // [4*hs, Kpad] bf16, zero past E + F; Kpad % 32 == 0
+  int Kpad;
+  const bf16_t* w_hh;                // [4*hs, hs] bf16
+  const float* bias;                 // [4*hs] fp32 = b_ih + b_hh
+  float* h_out; float* c_out;        // [B, hs] fp32 (h_out must not alias h_prev)
+  float* sv_gates; float* sv_c; bf16_t* sv_h;   // optional training saves, contiguous: [B, 4*hs], [B, hs], [B, hs]
+  int* err;                          // device flag raised by an id outside [0, A), or null
+  int B, hs;
+};
+
+// The action head of one turn-based step (turn_based.hip).
+struct TbHeadArgs {
+  const float* logit; long ld;               // [B, A] fp32, A <= 64 (not modified)
+  const long* target;                        // [B]
+  const unsigned char* blocked; long ld_blk; // [B, A] or null: non-zero = the logit counts as -inf
+  long ignore_index;
+  int B, A, mode;                            // mode: 0 teacher, 1 argmax, 2 sample
+  uint32_t seed;
+  float* loss; float* count;                 // [1] each: mean loss over the counted rows, number of counted rows
+  long* a_t;                                 // [B] next action (optional for mode 0)
+  int* err;                                  // device flag raised by a target outside [0, A) that is not ignore_index
+};
+
+struct TbHeadBwdArgs {
+  const float* logit; long ld;
+  const long* target;
+  const unsigned char* blocked; long ld_blk;
+  long ignore_index;
+  int B, A;
+  const float* g; const float* count;        // [1] each, on the device: gradient of the loss, the forward's count
+  float* dlogit; long ld_d;                  // [B, A] fp32
+};

@@ -1713,6 +1713,114 @@ def softdot_attention_bwd(target, context, mask, d_weighted, d_attn, output_prob
     return d_target, d_ctx
 
 
+# ---- the turn-based decoder step (tasks/turn_based/agent_models.py:277-319, agent.py:307-338; csrc/turn_based.hip) ------
+def turn_lstm_cell(first, feature, h_prev, c_prev, w_ih_pad, w_hh, bias, h_out=None, c_out=None, save=False, err_flag=None):
+    """nn.Embedding + cat + nn.LSTMCell in one launch.  first = (ids int64 [B], table fp32 [A, E]) or a ready fp32 [B, E]
+    block; feature fp32 [B, F]; rows of table / block / feature may be strided views (last dim contiguous) of any width.
+    w_ih_pad bf16 [4hs, Kpad] zero past E + F (Kpad a multiple of 32), w_hh bf16 [4hs, hs], bias fp32 [4hs] = b_ih + b_hh.
+    h_prev / c_prev fp32 [B, hs] contiguous and left as they are -> (h_1, c_1, saved | None), saved = (activated gates fp32
+    [B, 4hs], c_prev fp32, h_prev bf16) as ops.lstm_step_bwd reads them (save=True allocates them, a tuple is written into).  An id outside the table: the row's embedding counts
+    as zero and err_flag (int32 [1]) is raised."""
+    if isinstance(first, (tuple, list)):
+        ids, table = first
+        x_emb = None
+        _require_hip(ids, table)
+        assert ids.dtype == torch.int64 and ids.dim() == 1 and ids.is_contiguous()
+        assert table.dtype == torch.float32 and table.dim() == 2 and table.stride(1) == 1
+        A, E = table.shape
+        B = ids.shape[0]
+    else:
+        ids = table = None
+        x_emb = first
+        _require_hip(x_emb)
+        assert x_emb.dtype == torch.float32 and x_emb.dim() == 2 and x_emb.stride(1) == 1
+        B, E = x_emb.shape
+        A = 0
+    _require_hip(feature, h_prev, c_prev, w_ih_pad, w_hh, bias, h_out, c_out, err_flag)
+    hs = h_prev.shape[1]
+    assert feature.dtype == torch.float32 and feature.dim() == 2 and feature.shape[0] == B and feature.stride(1) == 1
+    F = feature.shape[1]
+    for s_ in (h_prev, c_prev):
+        assert s_.dtype == torch.float32 and s_.shape == (B, hs) and s_.is_contiguous()
+    assert w_ih_pad.dtype == BF16 and w_ih_pad.shape[0] == 4 * hs and w_ih_pad.stride(1) == 1
+    assert w_hh.dtype == BF16 and w_hh.shape == (4 * hs, hs) and w_hh.is_contiguous()
+    assert bias.dtype == torch.float32 and bias.shape == (4 * hs,) and bias.is_contiguous()
+    dev = h_prev.device
+    if h_out is None:
+        h_out = torch.empty((B, hs), dtype=torch.float32, device=dev)
+    if c_out is None:
+        c_out = torch.empty((B, hs), dtype=torch.float32, device=dev)
+    for s_ in (h_out, c_out):
+        assert s_.dtype == torch.float32 and s_.shape == (B, hs) and s_.is_contiguous()
+    saved = None
+    if isinstance(save, (tuple, list)):   # the caller's buffers
+        saved = tuple(save)
+        for s_, shp, dt in zip(saved, ((B, 4 * hs), (B, hs), (B, hs)), (torch.float32, torch.float32, BF16)):
+            _require_hip(s_)
+            assert s_.dtype == dt and s_.shape == shp and s_.is_contiguous()
+        save = True
+    elif save:
+        saved = (torch.empty((B, 4 * hs), dtype=torch.float32, device=dev), torch.empty((B, hs), dtype=torch.float32, device=dev),
+                 torch.empty((B, hs), dtype=BF16, device=dev))
+    if err_flag is not None:
+        assert err_flag.dtype == torch.int32 and err_flag.numel() == 1
+    Kpad = w_ih_pad.shape[1]
+    with _timed("turn_lstm_cell", 2.0 * B * 4 * hs * (E + F + hs), 2.0 * 4 * hs * (Kpad + hs)):
+        rc = _lib.load().vt_turn_lstm_cell_f32(
+            _ptr(ids), _ptr(table), 0 if table is None else table.stride(0), A, _ptr(x_emb),
+            0 if x_emb is None else x_emb.stride(0), E, _ptr(feature), feature.stride(0), F, _ptr(h_prev), _ptr(c_prev),
+            _ptr(w_ih_pad), w_ih_pad.stride(0), Kpad, _ptr(w_hh), _ptr(bias), _ptr(h_out), _ptr(c_out),
+            _ptr(saved[0]) if save else None, _ptr(saved[1]) if save else None, _ptr(saved[2]) if save else None,
+            _ptr(err_flag), B, hs, _stream())
+    _lib.check(rc, "vt_turn_lstm_cell_f32")
+    return h_out, c_out, saved
+
+
+TURN_FEEDBACK = {"teacher": 0, "argmax": 1, "sample": 2}
+
+
+def _blocked_u8(blocked, B, A):
+    if blocked is None:
+        return None
+    assert blocked.shape == (B, A)
+    b8 = blocked if blocked.dtype == torch.uint8 else blocked.to(torch.bool).view(torch.uint8)
+    return b8 if b8.stride(1) == 1 else b8.contiguous()
+
+
+def turn_action_head(logit, target, blocked, ignore_index, mode, seed, err_flag=None):
+    """One step's cross entropy and next action: logit fp32 [B, A] (A <= 64, row stride free, not modified), target int64
+    [B], blocked bool / uint8 [B, A] or None -> (loss fp32 [1], count fp32 [1], a_t int64 [B])."""
+    _require_hip(logit, target, blocked, err_flag)
+    assert logit.dtype == torch.float32 and logit.dim() == 2 and logit.stride(1) == 1
+    B, A = logit.shape
+    assert target.dtype == torch.int64 and target.shape == (B,) and target.is_contiguous()
+    b8 = _blocked_u8(blocked, B, A)
+    loss = torch.empty((1,), dtype=torch.float32, device=logit.device)
+    count = torch.empty((1,), dtype=torch.float32, device=logit.device)
+    a_t = torch.empty((B,), dtype=torch.int64, device=logit.device)
+    with _timed("turn_action_head", 0.0, 8.0 * B * A):
+        rc = _lib.load().vt_turn_action_head_f32(
+            _ptr(logit), logit.stride(0), _ptr(target), _ptr(b8), 0 if b8 is None else b8.stride(0), int(ignore_index), B, A,
+            int(mode), int(seed) & 0xFFFFFFFF, _ptr(loss), _ptr(count), _ptr(a_t), _ptr(err_flag), _stream())
+    _lib.check(rc, "vt_turn_action_head_f32")
+    return loss, count, a_t
+
+
+def turn_action_head_bwd(logit, target, blocked, ignore_index, g, count):
+    """dlogit fp32 [B, A] of turn_action_head's loss; g fp32 [1] (device) is the loss's gradient, count what the forward left."""
+    _require_hip(logit, target, blocked, g, count)
+    B, A = logit.shape
+    b8 = _blocked_u8(blocked, B, A)
+    assert g.dtype == torch.float32 and g.numel() == 1 and count.dtype == torch.float32 and count.numel() == 1
+    dlogit = torch.empty((B, A), dtype=torch.float32, device=logit.device)
+    with _timed("turn_action_head_bwd", 0.0, 8.0 * B * A):
+        rc = _lib.load().vt_turn_action_head_bwd_f32(
+            _ptr(logit), logit.stride(0), _ptr(target), _ptr(b8), 0 if b8 is None else b8.stride(0), int(ignore_index), B, A,
+            _ptr(g), _ptr(count), _ptr(dlogit), dlogit.stride(0), _stream())
+    _lib.check(rc, "vt_turn_action_head_bwd_f32")
+    return dlogit
+
+
 # ---- fp32 parity path (csrc/fp32_path.hip): every operand, activation and accumulation in fp32 -----------------------
 def _f32ok(*ts):
     for t in ts:
