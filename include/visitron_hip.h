@@ -576,6 +576,38 @@ int vt_turn_action_head_bwd_f32(const float* logit, int64_t ld, const int64_t* t
                                 int64_t ignore_index, int B, int A, const float* g, const float* count, float* dlogit,
                                 int64_t ld_d, vt_stream_t stream);
 
+/* ---- the rollout's observation tensors from a device feature store (ABI 20): tasks/viewpoint_select/agent.py:186-228 ----------
+ *
+ * store fp32 [N, V, D] contiguous (16-byte aligned base): the image features of N viewpoints, V views each.  table fp32
+ * [V, V, 4] (16-byte aligned): table[base view][view] = sin h, cos h, sin e, cos e of that view seen from the base view.
+ * record: one step's staged indices and angles, 8-byte aligned, laid out for B rows and Cmax candidate columns as
+ *   int32  rows[B][3]          slot, view_index, cand_count of every agent            at byte 0
+ *   int32  cand_point[B][Cmax]                                                        at byte 12 B
+ *   double agent[B][2]         heading, elevation                                     at byte round_up(12 B + 4 B Cmax, 8)
+ *   double cand_heading[B][Cmax], then double cand_elevation[B][Cmax]                 behind it
+ * One launch writes all five outputs (contiguous, 4-byte aligned):
+ *   input_a_t      fp32 [B, 4]         = sin, cos of heading, elevation, computed in float64 and rounded once
+ *   f_t            fp32 [B, V, D+4]    f_t[b, v] = [store[slot_b, v, :] | table[view_index_b, v, :]]
+ *   candidate_feat fp32 [B, Cmax, D+4] row j < cand_count_b = [store[slot_b, cand_point[b, j], :] | sin, cos of cand_heading,
+ *                                      cand_elevation[b, j] in float64, rounded once]; rows j >= cand_count_b (the END row and
+ *                                      the padding) are zero
+ *   candidate_leng int32 [B]           = cand_count_b + 1 (clamped into [1, Cmax])
+ *   candidate_mask uint8 [B, Cmax]     = j > candidate_leng_b - 1
+ * A row with slot outside [0, N), view_index outside [0, V), cand_count outside [0, Cmax) or a cand_point[b, j < cand_count_b]
+ * outside [0, V) gets every float output of that agent written as zeros and sets *err_flag (optional) to 1; nothing outside
+ * store, table and record is read.  D % 4 == 0 with f_t and candidate_feat 16-byte aligned moves 16-byte pieces; anything
+ * else goes element by element. */
+int vt_obs_gather_f32(const float* store, int64_t N, int V, int D, const float* table, const void* record, int B, int Cmax,
+                      float* input_a_t, float* f_t, float* candidate_feat, int32_t* candidate_leng, uint8_t* candidate_mask,
+                      int32_t* err_flag, vt_stream_t stream);
+
+/* The turn-based task's one view per row (tasks/turn_based/agent.py:197-210): out[b, :] = store[slot_b, view_index_b, :].
+ * rows int32 [B][2] = slot, view_index on the device (4-byte aligned); out fp32 [B, D] with row stride ld_out >= D.  A slot
+ * or view_index out of range: that row is zero and *err_flag (optional) is set to 1.  D % 4 == 0, ld_out % 4 == 0 and a
+ * 16-byte aligned out move 16-byte pieces. */
+int vt_obs_gather_view_f32(const float* store, int64_t N, int V, int D, const int32_t* rows, int B, float* out,
+                           int64_t ld_out, int32_t* err_flag, vt_stream_t stream);
+
 /* out[c, r] = in[r, c] (bf16; R, C multiples of 8): refreshes the transposed weight copies (W^T of every nn.Linear on the
  * path, oscar/modeling_bert.py:43-45,94,119,120) that the
  * dgrad GEMMs consume (vt_layer_weights_t). */

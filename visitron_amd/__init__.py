@@ -24,4 +24,8 @@ def __getattr__(name):  # lazy: importing the package must not require torch+HIP
         from . import ops
 
         return getattr(ops, name)
+    if name in ("FeatureStore", "default_view_angle_table"):   # the rollout's observation tensors from a device feature store
+        from . import observations
+
+        return getattr(observations, name)
     raise AttributeError(name)

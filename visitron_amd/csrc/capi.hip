@@ -21,7 +21,7 @@ const char* vt_error_string(int code) {
   }
 }
 
-int vt_abi_version(void) { return 19; }
+int vt_abi_version(void) { return 20; }
 
 // deterministic training mode (common.hpp): one word for the process, read by every dispatch at launch time
 void vt_set_deterministic(int on) { vt_deterministic_word().store(on ? 1 : 0, std::memory_order_relaxed); }
@@ -401,6 +401,33 @@ int vt_turn_action_head_bwd_f32(const float* logit, int64_t ld, const int64_t* t
   a.logit = logit; a.ld = ld; a.target = (const long*)target; a.blocked = blocked; a.ld_blk = ld_blk;
   a.ignore_index = ignore_index; a.B = B; a.A = A; a.g = g; a.count = count; a.dlogit = dlogit; a.ld_d = ld_d;
   return vt_tb_action_head_bwd_dispatch(a, (hipStream_t)stream);
+}
+
+int vt_obs_gather_f32(const float* store, int64_t N, int V, int D, const float* table, const void* record, int B, int Cmax,
+                      float* input_a_t, float* f_t, float* candidate_feat, int32_t* candidate_leng, uint8_t* candidate_mask,
+                      int32_t* err_flag, vt_stream_t stream) {
+  if (!record) return VT_ERR_NULL;
+  if (B <= 0 || Cmax < 1) return VT_ERR_BAD_SHAPE;
+  if (((uintptr_t)record) & 7) return VT_ERR_BAD_ALIGN;
+  // the record's layout (include/visitron_hip.h): int32 rows[B][3], int32 cand_point[B][Cmax], then the doubles, 8-byte aligned
+  const char* rec = (const char*)record;
+  const long nb = (long)B, nc = (long)B * Cmax;
+  const long off_f64 = (12 * nb + 4 * nc + 7) & ~7L;
+  ObsGatherArgs a;
+  a.store = store; a.N = N; a.V = V; a.D = D; a.table = table;
+  a.rows = (const int*)rec; a.pts = (const int*)(rec + 12 * nb);
+  a.agent = (const double*)(rec + off_f64); a.cand_h = a.agent + 2 * nb; a.cand_e = a.cand_h + nc;
+  a.B = B; a.Cmax = Cmax; a.a_t = input_a_t; a.f_t = f_t; a.cand = candidate_feat; a.leng = (int*)candidate_leng;
+  a.mask = candidate_mask; a.err = (int*)err_flag;
+  return vt_obs_gather_dispatch(a, (hipStream_t)stream);
+}
+
+int vt_obs_gather_view_f32(const float* store, int64_t N, int V, int D, const int32_t* rows, int B, float* out,
+                           int64_t ld_out, int32_t* err_flag, vt_stream_t stream) {
+  ObsViewArgs a;
+  a.store = store; a.N = N; a.V = V; a.D = D; a.rows = (const int*)rows; a.B = B; a.out = out; a.ld_out = ld_out;
+  a.err = (int*)err_flag;
+  return vt_obs_gather_view_dispatch(a, (hipStream_t)stream);
 }
 
 int vt_transpose_bf16(const void* in, int64_t ldi, void* out, int64_t ldo, int R, int C, vt_stream_t stream) {

@@ -197,6 +197,10 @@ int vt_tb_lstm_cell_dispatch(const TbCellArgs& a, hipStream_t stream);
 int vt_tb_action_head_dispatch(const TbHeadArgs& a, hipStream_t stream);
 int vt_tb_action_head_bwd_dispatch(const TbHeadBwdArgs& a, hipStream_t stream);
 
+// ---- observations.hip
+int vt_obs_gather_dispatch(const ObsGatherArgs& a, hipStream_t stream);
+int vt_obs_gather_view_dispatch(const ObsViewArgs& a, hipStream_t stream);
+
 // ---- rowops.hip: LayerNorm, embeddings, losses, optimizer and the other row kernels
 int vt_layernorm_dispatch(const void* x, long ldx, void* y, long ldy, const float* gamma, const float* beta,
                           float* mean, float* rstd, int M, int H, float eps, int grp_rows, int grp_stride,

@@ -118,3 +118,25 @@ struct TbHeadBwdArgs {
   const float* g; const float* count;        // [1] each, on the device: gradient of the loss, the forward's count
   float* dlogit; long ld_d;                  // [B, A] fp32
 };
+
+// The rollout's observation tensors gathered from the device feature store (observations.hip).
+struct ObsGatherArgs {
+  const float* store; long N; int V, D;      // [N, V, D] fp32
+  const float* table;                        // [V, V, 4] fp32: [base view][view][sin h, cos h, sin e, cos e]
+  const int* rows;                           // the staged record's parts: [B][3] slot, view_index, cand_count
+  const int* pts;                            // [B][Cmax] candidate views
+  const double* agent;                       // [B][2] heading, elevation
+  const double* cand_h; const double* cand_e;   // [B][Cmax] each
+  int B, Cmax;
+  float* a_t; float* f_t; float* cand;       // [B, 4], [B, V, D+4], [B, Cmax, D+4]
+  int* leng; unsigned char* mask;            // [B], [B, Cmax]
+  int* err;                                  // device flag raised by a bad index, or null
+};
+
+struct ObsViewArgs {
+  const float* store; long N; int V, D;
+  const int* rows;                           // [B][2] slot, view_index
+  int B;
+  float* out; long ld_out;                   // [B, D] fp32
+  int* err;
+};

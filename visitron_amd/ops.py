@@ -1821,6 +1821,61 @@ def turn_action_head_bwd(logit, target, blocked, ignore_index, g, count):
     return dlogit
 
 
+# ---- the rollout's observation tensors from a device feature store (csrc/observations.hip) ------------------------------------
+def obs_record_bytes(B, Cmax):
+    """Size of one step's staged record (include/visitron_hip.h, vt_obs_gather_f32) and the byte offset of its doubles."""
+    off_f64 = round_up(12 * B + 4 * B * Cmax, 8)
+    return off_f64 + 8 * (2 * B + 2 * B * Cmax), off_f64
+
+
+def obs_gather(store, table, record, B, Cmax, out=None, err_flag=None):
+    """One launch for a panoramic step's inputs.  store fp32 [N, V, D], table fp32 [V, V, 4], record uint8 [>= record bytes]
+    on the device (8-byte aligned, laid out as vt_obs_gather_f32 says) -> (input_a_t fp32 [B, 4], f_t fp32 [B, V, D+4],
+    candidate_feat fp32 [B, Cmax, D+4], candidate_leng int32 [B], candidate_mask bool [B, Cmax]).  out: the five tensors to
+    write into (contiguous), else they are allocated."""
+    _require_hip(store, table, record, err_flag)
+    assert store.dtype == torch.float32 and store.dim() == 3 and store.is_contiguous()
+    N, V, D = store.shape
+    assert table.dtype == torch.float32 and tuple(table.shape) == (V, V, 4) and table.is_contiguous()
+    assert record.dtype == torch.uint8 and record.dim() == 1 and record.numel() >= obs_record_bytes(B, Cmax)[0]
+    dev = store.device
+    if out is None:
+        out = (torch.empty((B, 4), dtype=torch.float32, device=dev), torch.empty((B, V, D + 4), dtype=torch.float32, device=dev),
+               torch.empty((B, Cmax, D + 4), dtype=torch.float32, device=dev), torch.empty((B,), dtype=torch.int32, device=dev),
+               torch.empty((B, Cmax), dtype=torch.bool, device=dev))
+    a_t, f_t, cand, leng, mask = out
+    for t, shp, dt in zip(out, ((B, 4), (B, V, D + 4), (B, Cmax, D + 4), (B,), (B, Cmax)),
+                          (torch.float32, torch.float32, torch.float32, torch.int32, torch.bool)):
+        _require_hip(t)
+        assert t.dtype == dt and tuple(t.shape) == shp and t.is_contiguous()
+    if err_flag is not None:
+        assert err_flag.dtype == torch.int32 and err_flag.numel() == 1
+    nbytes = 4.0 * B * (V + Cmax) * (D + 4)
+    with _timed("obs_gather", 0.0, 2.0 * nbytes):
+        rc = _lib.load().vt_obs_gather_f32(_ptr(store), N, V, D, _ptr(table), _ptr(record), B, Cmax, _ptr(a_t), _ptr(f_t),
+                                           _ptr(cand), _ptr(leng), _ptr(mask), _ptr(err_flag), _stream())
+    _lib.check(rc, "vt_obs_gather_f32")
+    return out
+
+
+def obs_gather_view(store, rows, B, out=None, err_flag=None):
+    """out[b] = store[slot_b, view_b, :].  rows int32 [B, 2] on the device; out fp32 [B, D] (row stride free)."""
+    _require_hip(store, rows, out, err_flag)
+    assert store.dtype == torch.float32 and store.dim() == 3 and store.is_contiguous()
+    N, V, D = store.shape
+    assert rows.dtype == torch.int32 and rows.numel() >= 2 * B and rows.is_contiguous()
+    if out is None:
+        out = torch.empty((B, D), dtype=torch.float32, device=store.device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (B, D) and out.stride(1) == 1
+    if err_flag is not None:
+        assert err_flag.dtype == torch.int32 and err_flag.numel() == 1
+    with _timed("obs_gather_view", 0.0, 8.0 * B * D):
+        rc = _lib.load().vt_obs_gather_view_f32(_ptr(store), N, V, D, _ptr(rows), B, _ptr(out), out.stride(0) if B > 1 else D,
+                                                _ptr(err_flag), _stream())
+    _lib.check(rc, "vt_obs_gather_view_f32")
+    return out
+
+
 # ---- fp32 parity path (csrc/fp32_path.hip): every operand, activation and accumulation in fp32 -----------------------
 def _f32ok(*ts):
     for t in ts:

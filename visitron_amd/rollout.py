@@ -435,3 +435,11 @@ class OscarEncoder(nn.Module):
         if hs * D != self.dec_hidden_size:
             c_t = _dense((c_t,), w["w_ct"], _f32c(self.encoder_lstm2decoder_ct.bias))                       # :300-301
         return ctx, decoder_init, c_t
+
+
+def action_feedback(logit, target, blocked=None, ignore_index=-100, feedback="teacher", seed=None):
+    """The panoramic loop's `logit.masked_fill_(candidate_mask, -inf)` + criterion + feedback (agent.py:396-425) in one launch:
+    `turn_based.action_feedback` serves [B, A <= 64] logits with a `blocked` mask, which is what the candidate mask is."""
+    from .turn_based import action_feedback as _action_feedback
+
+    return _action_feedback(logit, target, blocked, ignore_index, feedback, seed)
