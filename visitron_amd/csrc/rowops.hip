@@ -1901,7 +1901,8 @@ int vt_batch_rows_dispatch(const BatchRowsArgs& a, int lists, hipStream_t stream
 //   l = log_softmax(z), m = log_softmax(l), loss = -sum_{valid b} m[b, y_b] / n_valid, accuracy = #(argmax l == y) / B,
 //   dz = g - exp(l) * rowsum(g),  g = (exp(m) - onehot(y)) * valid * grad_scale / n_valid
 // (torch: two log_softmax, gather, clamp, exp, scatter_add, several multiplies and reductions = ~20 launches on a [256, 36]
-// tensor).  One workgroup, one wave per row in turn; A <= 64.  n_valid = 0 gives the NaN torch gives.
+// tensor).  One workgroup, one wave per row in turn; A <= 64.  n_valid = 0 gives the NaN loss torch gives and, as torch,
+// a gradient of zeros (an ignored row never gets a gradient).
 template <typename DZ>
 __global__ __launch_bounds__(1024) void action_head_rows(const float* __restrict__ z, long ldz, const long* __restrict__ y, int B,
                                                          int A, float grad_scale, DZ* __restrict__ dz, long lddz, int Ap,
@@ -1939,8 +1940,9 @@ __global__ __launch_bounds__(1024) void action_head_rows(const float* __restrict
       if (valid) loss -= m_y;
       hits += (long)amax == yb ? 1.f : 0.f;
     }
-    // (exp(m) - onehot) * valid * (grad_scale / n_valid); an ignored row is 0 * (grad_scale / n_valid): NaN only when n_valid = 0
-    const float g = lane < A ? (__expf(m) - (lane == yc ? 1.f : 0.f)) * ((valid ? 1.f : 0.f) * (grad_scale * inv_n)) : 0.f;
+    // (exp(m) - onehot) * (grad_scale / n_valid) on a valid row; an ignored row has weight 0 whatever n_valid is (torch's nll_loss
+    // backward writes only the rows that are not ignored: with n_valid = 0 the loss is NaN and the gradient exactly 0)
+    const float g = lane < A ? (__expf(m) - (lane == yc ? 1.f : 0.f)) * (valid ? grad_scale * inv_n : 0.f) : 0.f;
     const float gs = wave_sum(g);
     const float d = g - __expf(l) * gs;
     if (lane < Ap) ce_store1(dz + b * lddz + lane, lane < A ? d : 0.f);

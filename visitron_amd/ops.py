@@ -958,16 +958,18 @@ def batch_row_lists(labels, token_labels, mask, B, S, n_w, n_t, n_keep, tiles):
     return idx_w, idx_t, lay
 
 
-def action_head(logits, next_action, A, grad_scale, Ap):
+def action_head(logits, next_action, A, grad_scale, Ap, dz=None):
     """logits fp32 [B, >= A], next_action int64 [B] -> (loss 0-d, accuracy 0-d, dlogits bf16 [B, Ap]): the action head's
-    double log-softmax cross entropy with its gradient (encoder.py:142-151, 387-391) in one launch."""
-    _require_hip(logits, next_action)
+    double log-softmax cross entropy with its gradient (encoder.py:142-151, 387-391) in one launch.  dz: the gradient's
+    destination, bf16 [B, Ap] with any row stride (a view of a wider buffer); a fresh tensor otherwise."""
+    _require_hip(logits, next_action, dz)
     assert logits.dtype == torch.float32 and logits.stride(1) == 1 and next_action.dtype == torch.int64
     B = logits.shape[0]
-    dl = torch.empty((B, Ap), dtype=BF16, device=logits.device)
+    dl = torch.empty((B, Ap), dtype=BF16, device=logits.device) if dz is None else dz
+    assert dl.dtype == BF16 and tuple(dl.shape) == (B, Ap) and (dl.stride(1) == 1 or Ap == 1)
     out = torch.empty(2, dtype=torch.float32, device=logits.device)
     rc = _lib.load().vt_action_head_f32(_ptr(logits), logits.stride(0), _ptr(next_action.contiguous()), B, int(A),
-                                        float(grad_scale), _ptr(dl), Ap, int(Ap), _ptr(out), _stream())
+                                        float(grad_scale), _ptr(dl), dl.stride(0), int(Ap), _ptr(out), _stream())
     _lib.check(rc, "vt_action_head_f32")
     return out[0], out[1], dl
 
@@ -2141,14 +2143,16 @@ def ce_double_softmax_rows_g32(z, y, V, dz, scale):
     return loss, amax
 
 
-def action_head_g32(logits, next_action, A, grad_scale, Ap):
-    """action_head with an fp32 gradient: -> (loss 0-d, accuracy 0-d, dlogits fp32 [B, Ap])."""
-    _require_hip(logits, next_action)
+def action_head_g32(logits, next_action, A, grad_scale, Ap, dz=None):
+    """action_head with an fp32 gradient: -> (loss 0-d, accuracy 0-d, dlogits fp32 [B, Ap]).  dz: the gradient's destination,
+    fp32 [B, Ap] with any row stride (a view of a wider buffer); a fresh tensor otherwise."""
+    _require_hip(logits, next_action, dz)
     assert logits.dtype == torch.float32 and logits.stride(1) == 1 and next_action.dtype == torch.int64
     B = logits.shape[0]
-    dl = torch.empty((B, Ap), dtype=torch.float32, device=logits.device)
+    dl = torch.empty((B, Ap), dtype=torch.float32, device=logits.device) if dz is None else dz
+    assert dl.dtype == torch.float32 and tuple(dl.shape) == (B, Ap) and (dl.stride(1) == 1 or Ap == 1)
     out = torch.empty(2, dtype=torch.float32, device=logits.device)
     rc = _lib.load().vt_action_head_g32(_ptr(logits), logits.stride(0), _ptr(next_action.contiguous()), B, int(A),
-                                        float(grad_scale), _ptr(dl), Ap, int(Ap), _ptr(out), _stream())
+                                        float(grad_scale), _ptr(dl), dl.stride(0), int(Ap), _ptr(out), _stream())
     _lib.check(rc, "vt_action_head_g32")
     return out[0], out[1], dl
