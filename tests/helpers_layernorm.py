@@ -1,6 +1,6 @@
 """fp64 reference, CPU rounding model, derived per-element bounds, exact constructions and the case table of the LayerNorm family:
 layernorm_rows / layernorm_rows_full, layernorm_bwd_rows / layernorm_bwd_rows_full with ln_bwd_reduce, embed_layernorm /
-embed_layernorm_bwd / embed_layernorm_f32 (csrc/rowops.hip, csrc/fp32_path.hip), layernorm_rows_f32 (fp32_path.hip), ln_bwd_f32
+embed_layernorm_bwd / embed_layernorm_f32 (csrc/layernorm.hip, csrc/fp32_path.hip), layernorm_rows_f32 (fp32_path.hip), ln_bwd_f32
 (fp32_train.hip), ln_apply_rows and ln_stream_init (ln_deferred.hip).
 
 Everything here is plain torch / numpy on the CPU in float64, taken from the bf16-, fp16- or fp32-exact inputs.
@@ -168,7 +168,7 @@ def _switch(name, env):
 
 
 def fwd_dispatch(H, grp_rows, xf16, env=None):
-    """vt_layernorm_dispatch (csrc/rowops.hip) restated: (kernel instantiation, rows per wave, workgroups of M rows -> count)."""
+    """vt_layernorm_dispatch (csrc/layernorm.hip) restated: (kernel instantiation, rows per wave, workgroups of M rows -> count)."""
     rpw = _switch("VT_LN_FWD_ROWS", env)
     if rpw > 0 and grp_rows == 0 and H in FULL_H:
         R = 2 if rpw >= 2 else 1

@@ -1,4 +1,4 @@
-"""fp64 references, CPU models and derived per-element error bounds for the loss heads of csrc/rowops.hip:
+"""fp64 references, CPU models and derived per-element error bounds for the loss heads of csrc/loss_heads.hip:
 ce_softmax_rows (two passes, online rescaled), ce_softmax_rows_reg<8|32> (row in registers), ce_double_softmax_rows and
 action_head_rows, each with bf16 and fp32 gradient rows.
 
@@ -134,7 +134,7 @@ def round_up(n, k):
 
 
 def ce_dispatch(Vpad):
-    """the kernel ce_softmax_launch picks (csrc/rowops.hip): by the padded width"""
+    """the kernel ce_softmax_launch picks (csrc/loss_heads.hip): by the padded width"""
     need = (Vpad + 1023) // 1024
     return "ce_softmax_rows_reg<8>" if need <= 8 else "ce_softmax_rows_reg<32>" if need <= 32 else "ce_softmax_rows"
 

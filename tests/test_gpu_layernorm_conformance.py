@@ -1,4 +1,4 @@
-"""The LayerNorm family (csrc/rowops.hip, fp32_path.hip, fp32_train.hip, ln_deferred.hip) against the float64 reference and the
+"""The LayerNorm family (csrc/layernorm.hip, fp32_path.hip, fp32_train.hip, ln_deferred.hip) against the float64 reference and the
 derived per-element bounds of tests/helpers_layernorm.py, through visitron_amd.ops only.  Alone:
 python -m pytest tests/test_gpu_layernorm_conformance.py -m gpu -q -s
 

@@ -1,4 +1,4 @@
-"""The loss heads (csrc/rowops.hip: ce_softmax_rows, ce_softmax_rows_reg<8|32>, ce_double_softmax_rows, action_head_rows; bf16 and
+"""The loss heads (csrc/loss_heads.hip: ce_softmax_rows, ce_softmax_rows_reg<8|32>, ce_double_softmax_rows, action_head_rows; bf16 and
 fp32 gradient rows) against the float64 reference and the derived per-element bounds of tests/helpers_loss.py, through
 visitron_amd.ops only.  Alone:  python -m pytest tests/test_gpu_loss_conformance.py -m gpu -q -s
 

@@ -47,7 +47,7 @@ struct AttnArgs {
   // third of its vector instructions re-deriving them from the hash).  keep_bits[((b*nh + h) * nqb + qb) * kpitch + key]:
   // bit j = keep(query 32 qb + j, key), nqb = ceil(S / 32), kpitch = S rounded up to 32.  Null: nothing written.
   uint32_t* keep_bits;
-  // Weight prefetch riding along (round 6, common.hpp vt_prefetch_role; rowops.hip has the why): the workgroups of the grid's
+  // Weight prefetch riding along (round 6; common.hpp has vt_prefetch_role and the why): the workgroups of the grid's
   // z-slices B .. gridDim.z - 1 compute no attention but read `pf`'s byte ranges -- the weights of the GEMMs that follow --
   // and drop them, which leaves the lines in the Infinity Cache.  pf.n == 0 / gridDim.z == B: none.
   PrefetchArgs pf;

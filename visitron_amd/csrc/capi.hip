@@ -55,7 +55,7 @@ int vt_batch_row_lists(const int64_t* labels, const int64_t* token_labels, const
 
 int vt_action_head_f32(const float* logits, int64_t ld, const int64_t* next_action, int B, int A, float grad_scale, void* dlogits,
                        int64_t ldd, int Ap, float* loss_acc, vt_stream_t stream) {
-  return vt_action_head_dispatch(logits, ld, (const long*)next_action, B, A, grad_scale, dlogits, ldd, Ap, loss_acc,
+  return vt_action_head_dispatch(logits, ld, (const long*)next_action, B, A, grad_scale, dlogits, ldd, Ap, loss_acc, 0,
                                  (hipStream_t)stream);
 }
 
@@ -251,12 +251,12 @@ int vt_cast_f32_to_bf16(const float* src, void* dst_bf16, int64_t n, float scale
 
 int vt_ce_softmax_rows(const float* z, int64_t ldz, const int64_t* y, float* loss_row, int64_t* amax, void* dz, int64_t lddz,
                        int64_t rows, int V, int Vpad, float scale, vt_stream_t stream) {
-  return vt_ce_softmax_dispatch(z, ldz, y, loss_row, amax, dz, lddz, rows, V, Vpad, scale, (hipStream_t)stream);
+  return vt_ce_softmax_dispatch(z, ldz, y, loss_row, amax, dz, lddz, rows, V, Vpad, scale, 0, (hipStream_t)stream);
 }
 
 int vt_ce_double_softmax_rows(const float* z, int64_t ldz, const int64_t* y, float* loss_row, int64_t* amax, void* dz,
                               int64_t lddz, int64_t rows, int V, int Vpad, float scale, vt_stream_t stream) {
-  return vt_ce_double_softmax_dispatch(z, ldz, y, loss_row, amax, dz, lddz, rows, V, Vpad, scale, (hipStream_t)stream);
+  return vt_ce_double_softmax_dispatch(z, ldz, y, loss_row, amax, dz, lddz, rows, V, Vpad, scale, 0, (hipStream_t)stream);
 }
 
 int vt_lstm_step_train_f32(const float* xproj, int64_t ldx, const float* h_prev, float* h_out, float* c, const void* w_hh,
@@ -647,18 +647,18 @@ int vt_dropout_rows_f32(const float* x, int64_t ldx, int grp_rows, int grp_strid
 
 int vt_ce_softmax_rows_g32(const float* z, int64_t ldz, const int64_t* y, float* loss_row, int64_t* amax, float* dz, int64_t lddz,
                            int64_t rows, int V, int Vpad, float scale, vt_stream_t stream) {
-  return vt_ce_softmax_dispatch2(z, ldz, y, loss_row, amax, dz, lddz, rows, V, Vpad, scale, 1, (hipStream_t)stream);
+  return vt_ce_softmax_dispatch(z, ldz, y, loss_row, amax, dz, lddz, rows, V, Vpad, scale, 1, (hipStream_t)stream);
 }
 
 int vt_ce_double_softmax_rows_g32(const float* z, int64_t ldz, const int64_t* y, float* loss_row, int64_t* amax, float* dz,
                                   int64_t lddz, int64_t rows, int V, int Vpad, float scale, vt_stream_t stream) {
-  return vt_ce_double_softmax_dispatch2(z, ldz, y, loss_row, amax, dz, lddz, rows, V, Vpad, scale, 1, (hipStream_t)stream);
+  return vt_ce_double_softmax_dispatch(z, ldz, y, loss_row, amax, dz, lddz, rows, V, Vpad, scale, 1, (hipStream_t)stream);
 }
 
 int vt_action_head_g32(const float* logits, int64_t ld, const int64_t* next_action, int B, int A, float grad_scale, float* dlogits,
                        int64_t ldd, int Ap, float* loss_acc, vt_stream_t stream) {
-  return vt_action_head_dispatch2(logits, ld, (const long*)next_action, B, A, grad_scale, dlogits, ldd, Ap, loss_acc, 1,
-                                  (hipStream_t)stream);
+  return vt_action_head_dispatch(logits, ld, (const long*)next_action, B, A, grad_scale, dlogits, ldd, Ap, loss_acc, 1,
+                                 (hipStream_t)stream);
 }
 
 // the two bounded-wait counters of the current device in one launch (gemm_wgrad_v8.hip)

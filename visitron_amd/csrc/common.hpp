@@ -43,7 +43,7 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
 __device__ __forceinline__ float bf16lo(uint32_t w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf16hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
 
-// Four elements of the fused AdamW (pytorch-transformers rule; see adamw_flat in rowops.hip): THE element arithmetic of the
+// Four elements of the fused AdamW (pytorch-transformers rule; see adamw_flat in optim.hip): THE element arithmetic of the
 // whole-slab kernel and of the sharded one (shard_adamw, optim.hip) -- one text, so the two leave the same bits.
 __device__ __forceinline__ void adamw_flat_x4(f32x4& pv, const f32x4 gv, f32x4& mv, f32x4& vv, float lr, float step_size,
                                               float b1, float b2, float eps, float wd, float grad_scale) {
@@ -345,9 +345,14 @@ __host__ __forceinline__ DropCfg vt_make_drop_attn(float p, uint64_t step_seed, 
   d.scale = pq > 0.f ? 1.0f / (1.0f - pq) : 1.0f;
   return d;
 }
-// ---- weight prefetch (round 6; rowops.hip has the why) -----------------------------------------------------------------
-// Up to four byte ranges that a kernel's spare workgroups (or a launch of their own) read and drop, so that the lines sit in
-// the Infinity Cache when the next GEMM's one round of tiles asks for them.
+// ---- weight prefetch (round 6) --------------------------------------------------------------------------------------------------
+// At small batch the layer GEMMs are ONE round of tiles whose K loop prefetches two K-steps ahead; a weight matrix that was last
+// touched a step ago comes from HBM, not from the Infinity Cache (the step streams ~1.5 GB of activations through its 256 MB
+// between two uses of a weight), and a K = 3 072 tile then stalls on most of its 48 dependent K-steps: FFN-down 45 us on warm
+// weights, 67 us in the step (tools/r6/pair_cold.py: distinct weights AND distinct activations per layer reproduce it, either
+// alone does not; reading W2 once before FFN-up gives the 12 us back).  vt_prefetch_role reads up to four byte ranges and drops
+// the data: what it leaves behind is the lines in the Infinity Cache (and in the L2 of the XCD that happened to read them).
+// The ranges are read by a kernel's spare workgroups or by a launch of their own (prefetch_ranges, layernorm.hip).
 struct PrefetchArgs {
   const void* p[4];
   long bytes[4];

@@ -164,7 +164,9 @@ int vt_ln_stream_init_dispatch(const float* x, long ldx, void* s16, long lds, vo
 long vt_lstm_persistent_ws_bytes(int B, int hs);
 int vt_lstm_persistent_dispatch(LstmPersistArgs a, void* ws, long ws_bytes, hipStream_t stream);
 
-// ---- optim.hip: multi-tensor Adam / AdamW, gradient norm and clip over a chunk table
+// ---- optim.hip: AdamW over one flat slab; multi-tensor Adam / AdamW, gradient norm and clip over a chunk table
+int vt_adamw_dispatch(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16, long n, float lr,
+                      float step_size, float b1, float b2, float eps, float wd, float grad_scale, hipStream_t stream);
 int vt_multi_adam_dispatch(const uint64_t* table, long n_chunks, const float* hyper, float grad_coef,
                            const float* grad_coef_dev, hipStream_t stream);
 int vt_multi_sumsq_dispatch(const uint64_t* table, long n_chunks, void* partials, hipStream_t stream);
@@ -201,7 +203,7 @@ int vt_tb_action_head_bwd_dispatch(const TbHeadBwdArgs& a, hipStream_t stream);
 int vt_obs_gather_dispatch(const ObsGatherArgs& a, hipStream_t stream);
 int vt_obs_gather_view_dispatch(const ObsViewArgs& a, hipStream_t stream);
 
-// ---- rowops.hip: LayerNorm, embeddings, losses, optimizer and the other row kernels
+// ---- layernorm.hip: the bf16 engine's LayerNorm and embedding LayerNorm, forward and backward
 int vt_layernorm_dispatch(const void* x, long ldx, void* y, long ldy, const float* gamma, const float* beta,
                           float* mean, float* rstd, int M, int H, float eps, int grp_rows, int grp_stride,
                           hipStream_t stream, int x_f16 = 0, void* y_f16 = nullptr, long ldyh = 0,
@@ -210,40 +212,36 @@ int vt_embed_layernorm_dispatch(const int64_t* ids, const int64_t* type_ids, con
                                 const float* pos, const float* type, const float* gamma, const float* beta, void* y,
                                 long ldy, int B, int T, int S, int H, int n_word, int n_pos, int n_type, float eps,
                                 int* err_flag, hipStream_t stream, const DropCfg* drop = nullptr);
-int vt_pack_concat_dispatch(const float* s0, int d0, const float* s1, int d1, void* out, int kpad, long rows,
-                            hipStream_t stream);
 int vt_layernorm_bwd_dispatch(const void* x, long ldx, const void* dy, long ldy, const float* gamma, void* dx, long lddx,
                               float* dgamma, float* dbeta, float* partial_ws, int M, int H, float eps, int accumulate,
                               hipStream_t stream, void* dx2 = nullptr, long lddx2 = 0, const DropCfg* drop = nullptr,
                               int x_f16 = 0, const PrefetchArgs* pf = nullptr);
-int vt_dgelu_mul_dispatch(const void* g, const void* h, void* out, long n, hipStream_t stream);
 int vt_embed_layernorm_bwd_dispatch(const int64_t* ids, const int64_t* type_ids, const int64_t* pos_ids, const float* word,
                                     const float* pos, const float* type, const float* gamma, const void* g, long ldg,
                                     float* de, float* dgamma, float* dbeta, float* partial_ws, int B, int T, int S, int H,
                                     int n_word, int n_pos, int n_type, float eps, int accumulate, hipStream_t stream,
                                     const DropCfg* drop = nullptr);
-int vt_adamw_dispatch(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16, long n, float lr,
-                      float step_size, float b1, float b2, float eps, float wd, float grad_scale, hipStream_t stream);
+
+// ---- loss_heads.hip: loss, argmax and gradient rows of the three heads (dz_f32: fp32 gradient rows instead of bf16)
+int vt_ce_softmax_dispatch(const float* z, long ldz, const int64_t* y, float* loss_row, int64_t* amax, void* dz, long lddz,
+                           long rows, int V, int Vpad, float scale, int dz_f32, hipStream_t stream);
+int vt_ce_double_softmax_dispatch(const float* z, long ldz, const int64_t* y, float* loss_row, int64_t* amax, void* dz, long lddz,
+                                  long rows, int V, int Vpad, float scale, int dz_f32, hipStream_t stream);
+int vt_action_head_dispatch(const float* z, long ldz, const long* y, int B, int A, float grad_scale, void* dz, long lddz, int Ap,
+                            float* out, int dz_f32, hipStream_t stream);
+
+// ---- rowops.hip: the glue kernels (packing, casts, transposes, dropout, table gradients, mask centring, batch row lists)
+int vt_pack_concat_dispatch(const float* s0, int d0, const float* s1, int d1, void* out, int kpad, long rows,
+                            hipStream_t stream);
+int vt_dgelu_mul_dispatch(const void* g, const void* h, void* out, long n, hipStream_t stream);
 int vt_scale_heads_dispatch(const void* x, long ldx, void* out, long ldo, long rows, int nh, const float* scale, hipStream_t stream);
 int vt_cast_scale_dispatch(const float* x, void* y, long n, float scale, hipStream_t stream);
 int vt_transpose_dispatch(const void* in, long ldi, void* out, long ldo, int R, int C, hipStream_t stream);
 int vt_transpose_batch_dispatch(const void* const* in, const long* ldi, void* const* out, const long* ldo, const int* R,
                                 const int* C, int n, hipStream_t stream);
-int vt_ce_softmax_dispatch2(const float* z, long ldz, const int64_t* y, float* loss_row, int64_t* amax, void* dz, long lddz,
-                            long rows, int V, int Vpad, float scale, int dz_f32, hipStream_t stream);
-int vt_ce_softmax_dispatch(const float* z, long ldz, const int64_t* y, float* loss_row, int64_t* amax, void* dz, long lddz,
-                           long rows, int V, int Vpad, float scale, hipStream_t stream);
-int vt_ce_double_softmax_dispatch2(const float* z, long ldz, const int64_t* y, float* loss_row, int64_t* amax, void* dz, long lddz,
-                                   long rows, int V, int Vpad, float scale, int dz_f32, hipStream_t stream);
-int vt_ce_double_softmax_dispatch(const float* z, long ldz, const int64_t* y, float* loss_row, int64_t* amax, void* dz, long lddz,
-                                  long rows, int V, int Vpad, float scale, hipStream_t stream);
 int vt_apply_dropout_dispatch(void* x, long ld, long rows, int cols, const DropCfg& d, hipStream_t stream);
 int vt_dropout_mask_dispatch(uint8_t* out, long n, const DropCfg& d, hipStream_t stream, int attn);
 int vt_embed_table_grad_dispatch(const int* sorted_ids, const long* perm, const float* de, long ld_de, float* grad, long ld_grad,
                                  long n, int H, long n_rows_table, long skip_id, float* scratch, int* flag, hipStream_t stream);
 int vt_center_mask_dispatch(const void* mask, int kind, long ldm, float* out, int B, int S, hipStream_t stream);
 int vt_batch_rows_dispatch(const BatchRowsArgs& a, int lists, hipStream_t stream);
-int vt_action_head_dispatch2(const float* z, long ldz, const long* y, int B, int A, float grad_scale, void* dz, long lddz, int Ap,
-                             float* out, int dz_f32, hipStream_t stream);
-int vt_action_head_dispatch(const float* z, long ldz, const long* y, int B, int A, float grad_scale, void* dz, long lddz, int Ap,
-                            float* out, hipStream_t stream);

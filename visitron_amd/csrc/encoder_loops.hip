@@ -2,7 +2,7 @@
 // keep between calls: the weight-prefetch policy and the backward's events.  capi.hip's vt_encoder_* entry points forward here.
 #include "dispatch.hpp"
 
-// ---- weight prefetch (rowops.hip has the why) ---------------------------------------------------------
+// ---- weight prefetch (the why: common.hpp, at vt_prefetch_role) ---------------------------------------
 // The loops read the next GEMMs' weights ahead of time in spare workgroups of kernels that are launched anyway.  Training:
 // mode 4 (default), in the LayerNorm forward kernels and the LayerNorm backward's reduce kernels, below VT_PREFETCH_MAX_ROWS
 // token rows (default 16 384: at B = 256 the K loops run three rounds per CU at the chip's power-limited rate and hide the

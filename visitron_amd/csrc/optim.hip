@@ -10,6 +10,10 @@
 // is capped and workgroups stride over the table: the launch count never depends on the list.  A chunk whose addresses
 // are all multiples of 16 moves 16 bytes per lane and finishes its last n % 4 elements one per lane; any other chunk
 // (a view that starts 4 bytes into a buffer) moves one element per lane.  The branch is uniform over the workgroup.
+//
+// Also here: shard_adamw / shard_settle, the optimizer sharded over data-parallel ranks (their own tables, below), and at
+// the end of the file adamw_flat, the pretrain engine's AdamW over one flat slab, whose bits shard_adamw reproduces.
+// adamw_flat stands at file scope, outside the anonymous namespace: recorded kernel statistics key on its symbol.
 #include "dispatch.hpp"
 
 namespace {
@@ -300,4 +304,58 @@ int vt_multi_scale_dispatch(const uint64_t* table, long n_chunks, const float* c
   if (((uintptr_t)table & 7) || ((uintptr_t)coef_dev & 3)) return VT_ERR_BAD_ALIGN;
   hipLaunchKernelGGL(multi_scale, dim3(grid_for(n_chunks)), dim3(kThreads), 0, stream, table, n_chunks, coef_dev);
   return launched();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Fused AdamW step over a flat fp32 parameter slab, the pytorch-transformers rule used by
+// tasks/viewpoint_select/pretrain.py:128-130,192:
+//   m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  p -= step_size * m / (sqrt(v) + eps);  p -= lr*wd*p
+// with step_size = lr * sqrt(1-b2^t) / (1-b1^t) computed on the host (eps is added to the UN-corrected
+// sqrt(v); the decoupled decay uses the already-moved p).  Also refreshes the bf16 working copy the
+// GEMMs read.  grad_scale multiplies g first (1/world_size for the data-parallel mean).
+// G16: the gradients arrive as bf16 (the data-parallel all-reduce ran on a bf16 copy of the slab: half the bytes over
+// xGMI); moments and master weights stay fp32.
+template <bool G16>
+__global__ __launch_bounds__(256) void adamw_flat(float* __restrict__ p, const void* __restrict__ g, float* __restrict__ m,
+                                                  float* __restrict__ v, bf16_t* __restrict__ p_bf16, long n4, float lr,
+                                                  float step_size, float b1, float b2, float eps, float wd,
+                                                  float grad_scale) {
+  const long stride = (long)gridDim.x * 256;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    f32x4 pv = ((f32x4*)p)[i], mv = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
+    f32x4 gv;
+    if (G16) {
+      const u32x2 w = ((const u32x2*)g)[i];
+      gv = (f32x4){bf16lo(w[0]), bf16hi(w[0]), bf16lo(w[1]), bf16hi(w[1])};
+    } else {
+      gv = ((const f32x4*)g)[i];
+    }
+    adamw_flat_x4(pv, gv, mv, vv, lr, step_size, b1, b2, eps, wd, grad_scale);
+    ((f32x4*)p)[i] = pv;
+    ((f32x4*)m)[i] = mv;
+    ((f32x4*)v)[i] = vv;
+    if (p_bf16) {
+      u32x2 o;
+      o[0] = pack_bf16x2(pv[0], pv[1]);
+      o[1] = pack_bf16x2(pv[2], pv[3]);
+      ((u32x2*)p_bf16)[i] = o;
+    }
+  }
+}
+
+int vt_adamw_dispatch(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16, long n, float lr,
+                      float step_size, float b1, float b2, float eps, float wd, float grad_scale, hipStream_t stream) {
+  if (!p || !g || !m || !v) return VT_ERR_NULL;
+  if (n <= 0 || (n % 4)) return VT_ERR_BAD_SHAPE;
+  if (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15 || ((uintptr_t)g & (g_is_bf16 ? 7 : 15)) || ((uintptr_t)p_bf16 & 7)) return VT_ERR_BAD_ALIGN;
+  const long n4 = n / 4;
+  long blocks = (n4 + 255) / 256;
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  if (g_is_bf16)
+    hipLaunchKernelGGL(adamw_flat<true>, dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, n4, lr,
+                       step_size, b1, b2, eps, wd, grad_scale);
+  else
+    hipLaunchKernelGGL(adamw_flat<false>, dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, n4, lr,
+                       step_size, b1, b2, eps, wd, grad_scale);
+  return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
 }
