@@ -16,13 +16,14 @@
 * data parallelism: one process per GPU, bucketed all-reduce of the flat gradient slab
   (``torch.distributed``; backend "nccl" = RCCL over xGMI), see ``visitron_amd.distributed``.
 """
+import collections
 import ctypes
 import math
 
 import torch
 import torch.nn.functional as F
 
-from . import _lib, ops, switches, training_f32
+from . import _lib, distributed, ops, switches, training_f32
 from .modeling import BertImgModelwithLocationEmbeds, PreTrainOscar, _i64, invalidate_packed_weights
 from .ops import ACT_MUL, ACT_GELU, ACT_NONE, ACT_TANH, BF16, round_up
 
@@ -112,8 +113,124 @@ class FlatParams(object):
 KEEP_BITS = switches.on("VT_ATTN_KEEP_BITS")
 
 
+# One encoder layer: table field -> parameter name under "bert.encoder.layer.<l>.".  The "w_*" fields are GEMM weights (the
+# bf16 engine reads them through the mirror and keeps a transposed copy "wt_*" of each), the others fp32 vectors.
+_LAYER_FIELDS = dict(
+    w_ao="attention.output.dense.weight", b_ao="attention.output.dense.bias",
+    ln1_g="attention.output.LayerNorm.weight", ln1_b="attention.output.LayerNorm.bias",
+    w_in="intermediate.dense.weight", b_in="intermediate.dense.bias",
+    w_out="output.dense.weight", b_out="output.dense.bias",
+    ln2_g="output.LayerNorm.weight", ln2_b="output.LayerNorm.bias")
+# ... and the packed projection: query | key | value lie adjacent in the slabs (FlatParams), so [3H, H] / [3H] are views
+# that start at the query's entry
+_LAYER_PACKED = dict(w_qkv="attention.self.%s.weight", b_qkv="attention.self.%s.bias")
+_QKV = ("query", "key", "value")
+
+
+def _layer_views(flat, l, w_slab, v_slab):
+    """{field: view} of encoder layer l, the GEMM weights taken from w_slab and the vectors from v_slab."""
+    pre = "bert.encoder.layer.%d." % l
+    out = {}
+    for k, pat in _LAYER_PACKED.items():
+        o, cnt, shp = flat.off[pre + pat % _QKV[0]]
+        out[k] = (w_slab if k.startswith("w_") else v_slab)[o:o + 3 * cnt].view((3 * shp[0],) + shp[1:])
+    for k, name in _LAYER_FIELDS.items():
+        out[k] = flat.view(w_slab if k.startswith("w_") else v_slab, pre + name)
+    return out
+
+
+# the layer's GEMM weights by name (what _layer_views takes from w_slab)
+_LAYER_WEIGHTS = [_LAYER_PACKED["w_qkv"] % x for x in _QKV] + [n for k, n in _LAYER_FIELDS.items() if k.startswith("w_")]
+
+
+# The head, pooler and region-projection parameters: (group, attribute path on the model, transposed copy).  A weight with a
+# transposed copy (a key of PretrainEngine.head_t; "" = none kept) is a GEMM operand the bf16 step reads through the mirror;
+# None marks what is read as fp32.  The groups are what one supervision signal feeds: without it (no supervised MLM row, no
+# token row, no next_action, no regions) the group's gradients are zero.  Rows outside "bert." exist with the heads only.
+_HEAD_TABLE = (
+    ("pooler", "bert.pooler.dense.weight", "pool"), ("pooler", "bert.pooler.dense.bias", None),
+    ("mlm", "mlmhead.predictions.transform.dense.weight", "tr"), ("mlm", "mlmhead.predictions.transform.dense.bias", None),
+    ("mlm", "mlmhead.predictions.transform.LayerNorm.weight", None), ("mlm", "mlmhead.predictions.transform.LayerNorm.bias", None),
+    ("mlm", "mlmhead.predictions.bias", None),
+    ("mlm", "mlmhead.predictions.decoder.weight", "dec"),   # tied: the word table itself (PretrainEngine._head_group)
+    ("token", "token_head.0.weight", "tok"), ("token", "token_head.0.bias", None),
+    ("action", "next_action.linear.weight", "act"), ("action", "next_action.linear.bias", None),
+    ("region", "bert.img_embedding.weight", ""), ("region", "bert.img_embedding.bias", None),
+    ("region", "bert.location_embeds.weight", ""), ("region", "bert.location_embeds.bias", None),
+    ("region", "bert.LayerNorm.weight", None), ("region", "bert.LayerNorm.bias", None),   # (with use_img_layernorm only)
+)
+_HEAD_GROUPS = ("mlm", "token", "action", "pooler")   # final before the encoder backward starts; "region" is not
+
+
+class TrunkState(object):
+    """What a trunk forward leaves for its consumers: the heads, the trunk backward, trunk_forward's outputs, the autograd
+    nodes and the fp32 step (training_f32 fills the same class).  Nothing else of a forward outlives it: a tensor whose
+    address a later launch reads is a field here or belongs to `bufs`.  Fields a path does not use stay None."""
+
+    __slots__ = (
+        # ---- shapes
+        "B",              # batch size
+        "T",              # text positions per sequence
+        "R",              # region positions per sequence (0 without img_feats)
+        "S",              # T + R
+        "H",              # hidden size
+        "I",              # intermediate size
+        "nh",             # attention heads
+        "L",              # encoder layers
+        "M",              # B * S, the padded row count
+        "Mr",             # rows the encoder ran on: M, or the compacted layout's count
+        # ---- layout
+        "dev",            # the step's device
+        "bufs",           # the (B, S) _TrainBuffers holding the saved activations
+        "lay",            # ops.SeqLayout of the compacted rows, None on the padded layout
+        "cls_rows",       # int64 [B]: row of each sequence's [CLS] in the layout in use
+        "serial",         # number of this forward: a backward must belong to the engine's latest one
+        # ---- masks
+        "enc_mask",       # what the attention kernels take: centered 2-D mask, additive 3-D bias, None (no mask / compacted)
+        "mask_additive",  # enc_mask is the additive [B, S, St] form
+        "hs",             # head_mask as per-layer head scales [L, ...], or None
+        "mask",           # fp32 step: the mask as its softmax kernel takes it
+        "mode",           # fp32 step: that kernel's mask mode (-1 none, 0 [B, S], 2 additive [B, S, S])
+        # ---- dropout
+        "p_h", "p_a",     # hidden / attention dropout probability of this forward (0 in eval)
+        "seed",           # seed of this forward / backward pair
+        # ---- inputs
+        "ids",            # input_ids int64 [B, T]
+        "tt", "pos_ids",  # token_type_ids / position_ids, int64 or None
+        "img",            # img_feats as given, None for a text-only batch
+        "a_img",          # region projection's packed operand [B*R, kpad] (fp32 step: [B*R, D + 128])
+        # ---- kept activations (beside those in bufs)
+        "img_pre",        # region rows in front of the image LayerNorm [B*R, H], None without use_img_layernorm
+        "x_enc",          # the encoder's input rows in the layout in use
+        "seq",            # the last layer's output rows (bf16; fp32 step: fp32 [M, H])
+        "cls_seq",        # compacted layout: the [CLS] rows of seq, gathered [B, H]
+        "pooled",         # pooler output fp32 [B, H]
+        "pooled_bf",      # its bf16 copy, the action head's operand
+        "e",              # fp32 step: the embedding sum in front of its LayerNorm [B*T, H]
+        "x0",             # fp32 step: the embedding output [M, H] (layer 0's saved input; read through layers[0]["x"])
+        "layers",         # fp32 step: per layer the dict of saved activations
+        # ---- supervised rows (forward_backward only)
+        "lab", "tl",            # labels / token_labels flattened, int64 [M]
+        "idx_w", "idx_t",       # the padded rows that carry a label / a token label
+        "rows_w", "rows_t",     # the same rows in the layout in use
+        "Ml", "Mt",             # their counts
+        # ---- history
+        "hist",           # _history_state of a forward with encoder_history_states, else None
+        "d_history",      # after trunk_backward: per layer dL/d(history[l]) fp32 [B, Sh, H] or None
+    )
+
+    def __init__(self, **fields):
+        for name in self.__slots__:
+            setattr(self, name, fields.pop(name, None))
+        if fields:
+            raise TypeError("TrunkState has no field %s" % ", ".join(sorted(fields)))
+
+
 class _TrainBuffers(object):
     """Per-(B,S) activation store and gradient scratch, plus the ctypes tables for the C loops."""
+
+    # the workspace buffers with one row per token (a caller that runs fewer rows slices these); the others are sized otherwise
+    ws_rowed = ("g_pre", "g_pre2", "g_mid", "g_ctx", "g_qkv", "g_pre_d", "g_pre2_d")
 
     def __init__(self, L, M, B, S, H, I, nh, dev):
         mk = lambda n: torch.empty((M, n), dtype=BF16, device=dev)
@@ -156,43 +273,38 @@ class _TrainBuffers(object):
         need = ops.attention_bwd_ws_bytes(B, S, nh, M)
         if need:  # attention backward over several key blocks: dQ in fp32 (one slab; one plane per key block when deterministic)
             self.ws_t["dq32"] = torch.empty(need // 4, dtype=torch.float32, device=dev)
-        self.ws = _lib.BwdWorkspace()
-        for k, v in self.ws_t.items():
-            setattr(self.ws, k, v.data_ptr())
         # second set of the buffers a layer's weight-gradient launch reads: with it the wgrad of layer l runs on a side
         # stream beside layer l-1's dgrad chain (vt_encoder_backward_overlap_bf16); the rest is shared
         self.ws_t_b = dict(self.ws_t)
-        for k, n in (("g_pre", H), ("g_pre2", H), ("g_mid", I), ("g_qkv", 3 * H), ("g_pre_d", H), ("g_pre2_d", H)):
-            self.ws_t_b[k] = mk(n)
-        self.ws_b = _lib.BwdWorkspace()
-        for k, v in self.ws_t_b.items():
-            setattr(self.ws_b, k, v.data_ptr())
+        for k in self.ws_rowed:
+            if k != "g_ctx":   # (read by the dgrad chain only)
+                self.ws_t_b[k] = mk(self.ws_t[k].shape[1])
+        self.ws, self.ws_b = self._workspace(self.ws_t), self._workspace(self.ws_t_b)
 
+    @staticmethod
+    def _workspace(tab, ws=None):
+        """The library's table of a workspace dict's addresses (a fresh one, or `ws` pointed at the dict's present tensors)."""
+        ws = _lib.BwdWorkspace() if ws is None else ws
+        for k, v in tab.items():
+            setattr(ws, k, v.data_ptr())
+        return ws
 
-def _fit_dq32(self):
-    """The dQ workspace follows ops.set_deterministic: called in front of every backward, it asks the library what the current
-    mode needs and grows the buffer (both workspace tables point at it) when the switch was turned on after the buffers
-    were built."""
-    need = ops.attention_bwd_ws_bytes(*self._dq32_shape)
-    have = self.ws_t.get("dq32")
-    if need and (have is None or have.numel() * 4 < need):
-        buf = torch.empty(need // 4, dtype=torch.float32, device=self.x0.device)
-        for tab, ws in ((self.ws_t, self.ws), (self.ws_t_b, self.ws_b)):
-            tab["dq32"] = buf
-            ws.dq32 = buf.data_ptr()
+    def fit_dq32(self):
+        """The dQ workspace follows ops.set_deterministic: called in front of every backward, it asks the library what the
+        current mode needs and grows the buffer (both workspace tables point at it) when the switch was turned on after the
+        buffers were built."""
+        need = ops.attention_bwd_ws_bytes(*self._dq32_shape)
+        have = self.ws_t.get("dq32")
+        if need and (have is None or have.numel() * 4 < need):
+            self.ws_t["dq32"] = self.ws_t_b["dq32"] = torch.empty(need // 4, dtype=torch.float32, device=self.x0.device)
+            self._workspace(self.ws_t, self.ws)
+            self._workspace(self.ws_t_b, self.ws_b)
 
-
-_TrainBuffers.fit_dq32 = _fit_dq32
-
-
-def _ctx_raw(self, layer):
-    """Per-layer buffer for the attention kernel's unscaled context (head_mask in training), allocated on first use."""
-    if layer not in self._ctx_raw:
-        self._ctx_raw[layer] = self._mk(self._H)
-    return self._ctx_raw[layer]
-
-
-_TrainBuffers.ctx_raw = _ctx_raw
+    def ctx_raw(self, layer):
+        """Per-layer buffer for the attention kernel's unscaled context (head_mask in training), allocated on first use."""
+        if layer not in self._ctx_raw:
+            self._ctx_raw[layer] = self._mk(self._H)
+        return self._ctx_raw[layer]
 
 
 def _history_state(history, B, H, L, dev):
@@ -213,6 +325,11 @@ def _history_state(history, B, H, L, dev):
                 need=[bool(h.requires_grad) for h in history], xs=[None] * L, qkv=[None] * L, keep=[None] * L, d=[None] * L)
 
 
+# one encoder layer of the bf16 engine: t = what the forward reads (GEMM weights in the mirror, vectors in the fp32 slab), gr =
+# the same fields in the gradient slab, wt = the transposed copies of the GEMM weights the dgrad GEMMs read
+_LayerViews = collections.namedtuple("_LayerViews", "t gr wt")
+
+
 class _TrunkOnly(torch.nn.Module):
     """A bare BertImgModelwithLocationEmbeds presented to the engine under the parameter names it has inside a
     PreTrainOscar ("bert." + name): train.py:47 hands `model.bert` to the rollout agent, which trains through it."""
@@ -221,13 +338,6 @@ class _TrunkOnly(torch.nn.Module):
         super().__init__()
         self.bert = trunk
         self.config = trunk.config
-
-
-class _State(object):
-    """The locals of a trunk forward that its backward reads (PretrainEngine._trunk_fwd / _trunk_bwd)."""
-
-    def __init__(self, d):
-        self.__dict__.update({k: v for k, v in d.items() if k != "self"})
 
 
 class PretrainEngine(object):
@@ -289,12 +399,10 @@ class PretrainEngine(object):
         self.shard_optimizer = bool(shard_optimizer)
         self.shard = self.shard_optimizer and self.world > 1
         if self.shard:
-            from .distributed import SHARD_WORLDS
-
-            if self.world not in SHARD_WORLDS:
+            if self.world not in distributed.SHARD_WORLDS:
                 raise ValueError("shard_optimizer=True serves world sizes %s (a bucket is cut into `world` pieces of whole "
                                  "8-element groups, and %d does not divide ALIGN / 8 = %d), not %d"
-                                 % (SHARD_WORLDS, self.world, ALIGN // 8, self.world))
+                                 % (distributed.SHARD_WORLDS, self.world, ALIGN // 8, self.world))
         if precision == "fp32" and self.world > 1:
             raise NotImplementedError("PretrainEngine(precision='fp32') serves one rank")
         self.flat = FlatParams(model, attach_grads=attach_grads, moments=not self.shard)
@@ -358,12 +466,11 @@ class PretrainEngine(object):
     def _build_tables(self):
         self._wt_batch = None
         m, f, cfg = self.model, self.flat, self.cfg
-        L, H, I = cfg.num_hidden_layers, cfg.hidden_size, cfg.intermediate_size
+        L, H = cfg.num_hidden_layers, cfg.hidden_size
         self.w_tab = (_lib.LayerWeights * L)()
         self.wt_tab = (_lib.LayerWeightsT * L)()
         self.g_tab = (_lib.LayerGrads * L)()
-        self._keep, self.wt = [], []
-        self._mirror_views = set()   # names of the entries the layer tables point at in the bf16 mirror
+        self._layers = []        # per layer: _LayerViews of the tensors the three tables point at
         self.layer_ranges = []   # per layer: [(start, end) in the decay region, (start, end) in the no-decay region]
         for i in range(L):
             pre = "bert.encoder.layer.%d." % i
@@ -372,50 +479,53 @@ class PretrainEngine(object):
             nod = [r_ for r_ in offs if r_[0] >= f.n_decay]
             self.layer_ranges.append([(min(a_ for a_, _ in dec), max(b_ for _, b_ in dec)),
                                       (min(a_ for a_, _ in nod), max(b_ for _, b_ in nod))])
-            qw, qb = pre + "attention.self.query.weight", pre + "attention.self.query.bias"
-            names = dict(
-                w_ao=pre + "attention.output.dense.weight", b_ao=pre + "attention.output.dense.bias",
-                ln1_g=pre + "attention.output.LayerNorm.weight", ln1_b=pre + "attention.output.LayerNorm.bias",
-                w_in=pre + "intermediate.dense.weight", b_in=pre + "intermediate.dense.bias",
-                w_out=pre + "output.dense.weight", b_out=pre + "output.dense.bias",
-                ln2_g=pre + "output.LayerNorm.weight", ln2_b=pre + "output.LayerNorm.bias")
-            t = dict(w_qkv=f.view(f.mirror, qw, 3 * H * H, (3 * H, H)), b_qkv=f.view(f.p, qb, 3 * H, (3 * H,)))
-            gr = dict(d_w_qkv=f.view(f.g, qw, 3 * H * H, (3 * H, H)), d_b_qkv=f.view(f.g, qb, 3 * H, (3 * H,)))
-            self._mirror_views.update(pre + "attention.self.%s.weight" % x for x in ("query", "key", "value"))
-            for k, n in names.items():
-                t[k] = f.view(f.mirror if k.startswith("w_") else f.p, n)
-                if k.startswith("w_"):
-                    self._mirror_views.add(n)
-                gr["d_" + k] = f.view(f.g, n)
-            wt = dict(wt_qkv=torch.empty((H, 3 * H), dtype=BF16, device=f.p.device),
-                      wt_ao=torch.empty((H, H), dtype=BF16, device=f.p.device),
-                      wt_in=torch.empty((H, I), dtype=BF16, device=f.p.device),
-                      wt_out=torch.empty((I, H), dtype=BF16, device=f.p.device))
-            self._keep.append((t, gr))
-            self.wt.append((t, wt))
-            for k, v in t.items():
-                setattr(self.w_tab[i], k, v.data_ptr())
-            for k, v in gr.items():
-                setattr(self.g_tab[i], k, v.data_ptr())
-            for k, v in wt.items():
-                setattr(self.wt_tab[i], k, v.data_ptr())
-        # non-encoder weights: bf16 mirror views and transposed copies
+            t, gr = _layer_views(f, i, f.mirror, f.p), _layer_views(f, i, f.g, f.g)
+            wt = {"wt_" + k[2:]: torch.empty(v.shape[::-1], dtype=BF16, device=f.p.device)
+                  for k, v in t.items() if k.startswith("w_")}
+            self._layers.append(_LayerViews(t, gr, wt))
+            for row, views, pre_ in ((self.w_tab[i], t, ""), (self.g_tab[i], gr, "d_"), (self.wt_tab[i], wt, "")):
+                for k, v in views.items():
+                    setattr(row, pre_ + k, v.data_ptr())
+        # non-encoder weights: transposed copies [H, rows padded to the GEMM tile] (a zero column tail) of _HEAD_TABLE's operands
         dev = f.p.device
-        self.head_t = dict(pool=torch.empty((H, H), dtype=BF16, device=dev))
+        # ([H, H] for the square ones; a head's few output rows are padded to the GEMM tile, the column tail stays zero)
+        self.head_t = {key: (torch.empty((H, H), dtype=BF16, device=dev) if prm.shape[0] == H else
+                             torch.zeros((H, round_up(prm.shape[0], 64)), dtype=BF16, device=dev))
+                       for _, prm, key in self._head_rows() if key}
         if self.has_heads:
-            V = m.mlmhead.predictions.decoder.weight.shape[0]
-            C = m.token_head[0].weight.shape[0]
-            A = m.next_action.linear.weight.shape[0]
-            self.Vp, self.Cp, self.Ap = round_up(V, 64), round_up(C, 64), round_up(A, 64)
-            self.head_t.update(
-                dec=torch.zeros((H, self.Vp), dtype=BF16, device=dev), tr=torch.empty((H, H), dtype=BF16, device=dev),
-                tok=torch.zeros((H, self.Cp), dtype=BF16, device=dev), act=torch.zeros((H, self.Ap), dtype=BF16, device=dev))
+            self.Vp, self.Cp, self.Ap = (self.head_t[k].shape[1] for k in ("dec", "tok", "act"))
         D = m.bert.img_dim
         self.kpad = round_up(D + 128, 64)
         self.w_img = torch.zeros((H, self.kpad), dtype=BF16, device=dev)
         self.b_img = torch.zeros(H, dtype=torch.float32, device=dev)
         self.dw_img = torch.zeros((H, self.kpad), dtype=torch.float32, device=dev)
         self.db_img = torch.zeros(H, dtype=torch.float32, device=dev)
+
+    def _head_rows(self, *groups):
+        """_HEAD_TABLE's rows (group, parameter, transposed copy) that exist in this model, of the named groups (all if none)."""
+        m, rows = self.model, []
+        for grp, path, key in _HEAD_TABLE:
+            if (groups and grp not in groups) or not (self.has_heads or path.startswith("bert.")):
+                continue
+            if path.startswith("bert.LayerNorm.") and not getattr(m.bert, "use_img_layernorm", None):
+                continue
+            rows.append((grp, m.get_parameter(path), key))
+        return rows
+
+    def _decoder_tied(self):
+        return self.model.mlmhead.predictions.decoder.weight is self.model.bert.embeddings.word_embeddings.weight
+
+    def _head_group(self, *groups):
+        """The parameters of the named _HEAD_TABLE groups whose gradients belong to that group alone: a tied MLM decoder IS
+        the word table, whose gradient the embedding backward also adds to -- it is zeroed, reduced and updated with the
+        embeddings, never with the heads."""
+        word = self.model.bert.embeddings.word_embeddings.weight
+        return [prm for _, prm, _ in self._head_rows(*groups) if prm is not word]
+
+    def _zero_head_grads(self, *groups):
+        """Zero gradients for the named groups: nothing in this step supervises them (both engines)."""
+        for prm in self._head_group(*groups):
+            self._grad(prm).zero_()
 
     def _name_of(self, param):
         for n, p, _, _, _ in self.flat.entries:
@@ -437,17 +547,9 @@ class PretrainEngine(object):
         if not self._wt_dirty:
             return
         m, D = self.model, self.model.bert.img_dim
-        if self._wt_batch is None:   # all layers' four matrices + the two square head matrices: one launch
-            pairs = []
-            for t, wt in self.wt:
-                pairs += [(t["w_qkv"], wt["wt_qkv"]), (t["w_ao"], wt["wt_ao"]), (t["w_in"], wt["wt_in"]),
-                          (t["w_out"], wt["wt_out"])]
-            pairs += [(self._mirror(m.bert.pooler.dense.weight), self.head_t["pool"])]
-            if self.has_heads:
-                pairs += [(self._mirror(m.mlmhead.predictions.transform.dense.weight), self.head_t["tr"]),
-                          (self._mirror(m.mlmhead.predictions.decoder.weight), self.head_t["dec"]),
-                          (self._mirror(m.token_head[0].weight), self.head_t["tok"]),
-                          (self._mirror(m.next_action.linear.weight), self.head_t["act"])]
+        if self._wt_batch is None:   # all layers' four matrices + the head matrices: one launch
+            pairs = [(lv.t["w_" + k[3:]], dst) for lv in self._layers for k, dst in lv.wt.items()]
+            pairs += [(self._mirror(prm), self.head_t[key]) for _, prm, key in self._head_rows() if key]
             self._wt_batch = ops.TransposeBatch(pairs)
         self._wt_batch.run()
         self.w_img[:, :D].copy_(self._mirror(m.bert.img_embedding.weight))
@@ -496,7 +598,7 @@ class PretrainEngine(object):
     # ------------------------------------------------------------------------------ forward + backward
     def _trunk_fwd(self, batch, head_mask, labels, token_labels, training, allow_compact, comm=None, history=None):
         """The trunk's forward (embeddings, region projection, encoder layers, pooler) with every activation the backward
-        needs kept in the (B, S) buffer set; returns the step's state (a namespace of the locals below).  labels /
+        needs kept in the (B, S) buffer set; returns the step's state (a TrunkState, filled field by field at the end).  labels /
         token_labels (optional): the supervised rows are located here, where the host synchronises anyway.
         history (optional): encoder_history_states, one [B, Sh, H] tensor per layer -- layer l's keys and values run over
         cat([history[l], hidden], 1) (oscar/modeling_bert.py:37-41, 148-155) and the mask covers those Sh + S keys."""
@@ -547,7 +649,6 @@ class PretrainEngine(object):
         seed = (self.drop_seed_base + self.fb_count) & 0xFFFFFFFFFFFFFFFF
         self.fb_count += 1
         self.last_drop_seed = seed
-        dp_kw = dict(p_hidden=p_h, p_attn=p_a, drop_seed=seed)
         # the text embeddings go first: their out-of-range flag is then ready when the host synchronises below
         err = torch.zeros(1, dtype=torch.int32, device=dev)
         ops.embed_layernorm(ids, tt, pos_ids, emb.word_embeddings.weight.detach(), emb.position_embeddings.weight.detach(),
@@ -627,7 +728,7 @@ class PretrainEngine(object):
 
         # ---------------- forward ----------------
         x0 = bufs.x0
-        a_img = None
+        a_img = img_pre = None
         if img is not None:
             a_img = ops.pack_concat(img.reshape(B * R, -1).float().contiguous(),
                                     batch["img_location_embeddings"].reshape(B * R, -1).float().contiguous(), self.kpad)
@@ -641,35 +742,31 @@ class PretrainEngine(object):
                     ops.apply_dropout(img_ln, (p_h, seed, ops.SITE_IMG))
                 x0.view(B, S, H)[:, T:].copy_(img_ln.view(B, R, H))
             else:
-                img_pre = None
                 ops.linear(a_img, self.w_img, self.b_img, out=x0[T:], ldc=H, grp_rows=R, grp_stride=S,
                            drop=(p_h, seed, ops.SITE_IMG))
         x_enc, enc_mask = x0, mask
         if lay is not None:
             x_enc, enc_mask = bufs.x0c[:Mr], None
             torch.index_select(x0, 0, lay.index, out=x_enc)
-        if hist is not None:
+        if hist is not None or ops.profiling() or hs is not None:
             self._encoder_forward_unrolled(bufs, x_enc, enc_mask, B, S, p_h, p_a, seed, lay, mask_additive, hs, hist=hist)
-        elif ops.profiling() or hs is not None:
-            self._encoder_forward_unrolled(bufs, x_enc, enc_mask, B, S, p_h, p_a, seed, lay, mask_additive, hs)
         else:
             ops.encoder_forward(self.w_tab, bufs.acts, x_enc, enc_mask, mask_additive, None, B, S, H, nh, I,
-                                cfg.layer_norm_eps, seq=lay, **dp_kw)
+                                cfg.layer_norm_eps, p_hidden=p_h, p_attn=p_a, drop_seed=seed, seq=lay)
         seq = bufs.layers[-1]["out"][:Mr]
-        if lay is None:
-            cls_seq = None
-            pooled = ops.linear(seq, self._mirror(m.bert.pooler.dense.weight), m.bert.pooler.dense.bias.detach(),
-                                act=ACT_TANH, out_f32=True, M=B, lda=S * H)
-        else:
-            cls_seq = seq.index_select(0, cls_rows)
-            pooled = ops.linear(cls_seq, self._mirror(m.bert.pooler.dense.weight), m.bert.pooler.dense.bias.detach(),
-                                act=ACT_TANH, out_f32=True)
-        pooled_bf = pooled.to(BF16)
-
+        # the [CLS] rows: every S-th row of the padded layout (a row stride), gathered from the compacted one
+        cls_seq = None if lay is None else seq.index_select(0, cls_rows)
+        pooled = ops.linear(seq if lay is None else cls_seq, self._mirror(m.bert.pooler.dense.weight),
+                            m.bert.pooler.dense.bias.detach(), act=ACT_TANH, out_f32=True,
+                            **(dict(M=B, lda=S * H) if lay is None else {}))
         self._fwd_serial += 1
-        st = _State(locals())
-        st.serial = self._fwd_serial
-        return st
+        return TrunkState(
+            B=B, T=T, R=R, S=S, H=H, I=I, nh=nh, L=L, M=M, Mr=Mr,
+            dev=dev, bufs=bufs, lay=lay, cls_rows=cls_rows, serial=self._fwd_serial,
+            enc_mask=enc_mask, mask_additive=mask_additive, hs=hs, p_h=p_h, p_a=p_a, seed=seed,
+            ids=ids, tt=tt, pos_ids=pos_ids, img=img, a_img=a_img, img_pre=img_pre,
+            x_enc=x_enc, seq=seq, cls_seq=cls_seq, pooled=pooled, pooled_bf=pooled.to(BF16),
+            lab=lab, tl=tl, idx_w=idx_w, idx_t=idx_t, rows_w=rows_w, rows_t=rows_t, Ml=Ml, Mt=Mt, hist=hist)
 
     def forward_backward(self, batch, grad_scale=1.0, accumulate=False, comm=None, head_mask=None, backward=True):
         """One forward + backward; gradients of `grad_scale * loss` land in the flat slab (p.grad).
@@ -682,19 +779,32 @@ class PretrainEngine(object):
                 raise NotImplementedError("PretrainEngine(precision='fp32') serves one rank")
             return training_f32.forward_backward(self, batch, grad_scale, accumulate, head_mask, backward)
         st = self._trunk_fwd(batch, head_mask, batch["labels"], batch["token_labels"], self.model.training, True, comm)
-        m, cfg, f, dev, emb, bufs = self.model, self.cfg, self.flat, st.dev, st.emb, st.bufs
-        B, S, H, Mr, lay = st.B, st.S, st.H, st.Mr, st.lay
-        seq, pooled, pooled_bf, cls_seq, cls_rows = st.seq, st.pooled, st.pooled_bf, st.cls_seq, st.cls_rows
-        lab, tl, idx_w, idx_t, rows_w, rows_t, Ml, Mt = st.lab, st.tl, st.idx_w, st.idx_t, st.rows_w, st.rows_t, st.Ml, st.Mt
-        next_action = batch.get("next_action")
+        out, kept = self._heads_forward(st, batch, grad_scale)
+        if not backward:   # train() under torch.no_grad(): the forward with its dropout, nothing else
+            return out
+        acc = bool(accumulate)
+        self._heads_backward(st, kept, acc)
+        if comm is not None:
+            # data-parallel: the head / pooler gradients are final here, before the encoder backward has started -- their
+            # all-reduce goes out first and hides under the whole backward (round 3 reduced them last, with the embeddings)
+            rng = self._param_ranges(self._head_params())
+            comm["launch"](rng)
+            comm["done"].extend(rng)
+        self._trunk_bwd(st, None, acc, comm, word_grad_ready=True)
+        return out
 
-        # heads on supervised rows only
+    def _heads_forward(self, st, batch, grad_scale):
+        """The heads on the supervised rows only -> (the reference's 7-tuple, what _heads_backward reads: per head a dict of
+        its operands and of d(grad_scale * loss) / d(logits), None for a head nothing supervises in this batch)."""
+        m, cfg, dev, seq = self.model, self.cfg, st.dev, st.seq
+        Ml, Mt, H = st.Ml, st.Mt, st.H
         V, C, A = cfg.vocab_size, cfg.detector_classes, cfg.action_space
         pr = m.mlmhead.predictions
         zero = torch.zeros((), dtype=torch.float32, device=dev)
+        mlm = tok = act = None
         if Ml > 0:
-            seq_w = seq.index_select(0, rows_w)
-            y_w = lab.index_select(0, idx_w)
+            seq_w = seq.index_select(0, st.rows_w)
+            y_w = st.lab.index_select(0, st.idx_w)
             h_t = torch.empty((Ml, H), dtype=BF16, device=dev)
             t1 = ops.linear(seq_w, self._mirror(pr.transform.dense.weight), pr.transform.dense.bias.detach(), act=ACT_GELU,
                             pre_act_out=h_t)
@@ -707,13 +817,13 @@ class PretrainEngine(object):
             loss_rows, amax_w = ops.ce_softmax_rows(logits, y_w, V, dl, float(grad_scale) / Ml)
             mask_loss = loss_rows.mean()
             words_acc = (amax_w == y_w).sum().float() / Ml
+            mlm = dict(x=seq_w, h_t=h_t, t1=t1, t2=t2, dl=dl)
         else:
-            mask_loss = zero / zero  # CrossEntropyLoss over no valid target is nan, as in the reference
-            words_acc = zero / zero
+            mask_loss, words_acc = zero / zero, zero / zero  # CrossEntropyLoss over no valid target is nan, as in the reference
         lin_tok = m.token_head[0]
         if Mt > 0:
-            seq_t = seq.index_select(0, rows_t)
-            y_t = tl.index_select(0, idx_t)
+            seq_t = seq.index_select(0, st.rows_t)
+            y_t = st.tl.index_select(0, st.idx_t)
             lt = torch.empty((Mt, self.Cp), dtype=torch.float32, device=dev)
             ops.linear(seq_t, self._mirror(lin_tok.weight), lin_tok.bias.detach(), out=lt, out_f32=True)
             # token_head = Linear + Softmax and the criterion applies log-softmax AGAIN: loss, argmax and the gradient
@@ -722,32 +832,37 @@ class PretrainEngine(object):
             tok_rows, amax_t = ops.ce_double_softmax_rows(lt, y_t, C, dlt, float(grad_scale) / Mt)
             token_loss = tok_rows.mean()
             token_acc = (amax_t == y_t).sum().float() / Mt
+            tok = dict(x=seq_t, dl=dlt)
         else:
-            token_loss = zero / zero
-            token_acc = zero / zero
-        la = torch.empty((B, self.Ap), dtype=torch.float32, device=dev)
-        ops.linear(pooled_bf, self._mirror(m.next_action.linear.weight), m.next_action.linear.bias.detach(), out=la,
+            token_loss, token_acc = zero / zero, zero / zero
+        la = torch.empty((st.B, self.Ap), dtype=torch.float32, device=dev)
+        ops.linear(st.pooled_bf, self._mirror(m.next_action.linear.weight), m.next_action.linear.bias.detach(), out=la,
                    out_f32=True)
-        dla_bf = None
+        next_action = batch.get("next_action")
         if next_action is not None:
             # LogSoftmax head under a CrossEntropyLoss that applies log_softmax again (encoder.py:142-151, 387-391): loss,
             # accuracy and d(grad_scale * loss)/d(logits) in one launch
             next_loss, action_acc, dla_bf = ops.action_head(la, _i64(next_action), A, float(grad_scale), self.Ap)
+            act = dict(dl=dla_bf)
         else:
             next_loss, action_acc = 0, 0
         loss = mask_loss + next_loss + token_loss
-        if not backward:   # train() under torch.no_grad(): the forward with its dropout, nothing else
-            return (loss, mask_loss, next_loss, token_loss, words_acc, action_acc, token_acc)
+        return (loss, mask_loss, next_loss, token_loss, words_acc, action_acc, token_acc), (mlm, tok, act)
 
-        # ---------------- backward ----------------
-        gs = float(grad_scale)
-        acc = bool(accumulate)
+    def _heads_backward(self, st, kept, acc):
+        """Back through the heads: their gradients into the flat slab (a head without supervision: zeros, unless the step
+        accumulates) and dL/d(sequence output) into bufs.g, where the trunk backward reads it."""
+        m, cfg, bufs = self.model, self.cfg, st.bufs
+        B, S, H, Ml, Mt, seq = st.B, st.S, st.H, st.Ml, st.Mt, st.seq
+        V, C, A = cfg.vocab_size, cfg.detector_classes, cfg.action_space
+        mlm, tok, act = kept
+        pr, lin_tok, emb = m.mlmhead.predictions, m.token_head[0], m.bert.embeddings
         # dL/d(sequence output): zero except at the supervised / [CLS] rows.  Assembled directly in the bf16 buffer the
         # encoder backward reads (a row normally belongs to one head; where two heads meet the sum is formed in bf16)
-        g16 = bufs.g[:Mr]
+        g16 = bufs.g[:st.Mr]
         g16.zero_()
         wg = lambda dy, x, dw, db: dict(dy=dy, x=x, dw=dw, db=db, accumulate=acc)
-        dec_w_is_tied = pr.decoder.weight is emb.word_embeddings.weight
+        dec_w_is_tied = self._decoder_tied()
         word_grad = self._grad(emb.word_embeddings.weight)
         # The word table's gradient receives the embedding backward's run sums later on (_trunk_bwd), so it must hold
         # defined values before that: with a tied decoder and supervised rows the decoder's weight gradient -- the first
@@ -757,7 +872,8 @@ class PretrainEngine(object):
             word_grad.zero_()
             if dec_w_is_tied:
                 self._grad(pr.bias).zero_()  # shares the accumulate flag of the tied decoder weight below
-        if Ml > 0:
+        if mlm is not None:
+            dl, t1, t2 = mlm["dl"], mlm["t1"], mlm["t2"]
             dec_grad = self._grad(pr.decoder.weight)
             ops.wgrad([dict(dy=dl[:, :V], x=t2, dw=dec_grad, db=self._grad(pr.bias),
                             accumulate=acc or (dec_w_is_tied and not dec_overwrites))], Ml)
@@ -767,52 +883,33 @@ class PretrainEngine(object):
             g_t1 = ops.layernorm_bwd(t1, g_t2, pr.transform.LayerNorm.weight.detach(), pr.transform.LayerNorm.variance_epsilon,
                                      self._grad(pr.transform.LayerNorm.weight), self._grad(pr.transform.LayerNorm.bias),
                                      ws=bufs.ws_t["ln_partial"], accumulate=acc)
-            g_ht = ops.dgelu_mul(g_t1, h_t)
-            ops.wgrad([wg(g_ht, seq_w, self._grad(pr.transform.dense.weight), self._grad(pr.transform.dense.bias))], Ml)
-            g16.index_add_(0, rows_w, ops.linear(g_ht, self.head_t["tr"]))
+            g_ht = ops.dgelu_mul(g_t1, mlm["h_t"])
+            ops.wgrad([wg(g_ht, mlm["x"], self._grad(pr.transform.dense.weight), self._grad(pr.transform.dense.bias))], Ml)
+            g16.index_add_(0, st.rows_w, ops.linear(g_ht, self.head_t["tr"]))
         elif not acc:
             # no supervised MLM row (the loss is NaN, as the reference's): the head's gradients must not keep the
-            # previous step's values (the tied decoder weight / bias were zeroed above)
-            for prm in (pr.transform.dense.weight, pr.transform.dense.bias, pr.transform.LayerNorm.weight,
-                        pr.transform.LayerNorm.bias, pr.bias) + (() if dec_w_is_tied else (pr.decoder.weight,)):
-                self._grad(prm).zero_()
-        if Mt > 0:
-            ops.wgrad([wg(dlt[:, :C], seq_t, self._grad(lin_tok.weight), self._grad(lin_tok.bias))], Mt)
-            g16.index_add_(0, rows_t, ops.linear(dlt, self.head_t["tok"]))
+            # previous step's values (a tied decoder's weight -- the word table -- was zeroed above)
+            self._zero_head_grads("mlm")
+        if tok is not None:
+            ops.wgrad([wg(tok["dl"][:, :C], tok["x"], self._grad(lin_tok.weight), self._grad(lin_tok.bias))], Mt)
+            g16.index_add_(0, st.rows_t, ops.linear(tok["dl"], self.head_t["tok"]))
         elif not acc:
-            self._grad(lin_tok.weight).zero_()
-            self._grad(lin_tok.bias).zero_()
-        if next_action is not None:
-            ops.wgrad([wg(dla_bf[:, :A], pooled_bf, self._grad(m.next_action.linear.weight),
+            self._zero_head_grads("token")
+        if act is not None:
+            dla_bf, pooled = act["dl"], st.pooled
+            ops.wgrad([wg(dla_bf[:, :A], st.pooled_bf, self._grad(m.next_action.linear.weight),
                           self._grad(m.next_action.linear.bias))], B)
             g_pooled = ops.linear(dla_bf, self.head_t["act"], out_f32=True)
             g_z = (g_pooled * (1.0 - pooled * pooled)).to(BF16)
-            ops.wgrad([dict(dy=g_z, x=seq.view(B, S * H)[:, :H] if lay is None else cls_seq,
-                            dw=self._grad(m.bert.pooler.dense.weight), db=self._grad(m.bert.pooler.dense.bias),
-                            accumulate=acc)], B)
-            g16.index_add_(0, cls_rows, ops.linear(g_z, self.head_t["pool"]))
+            ops.wgrad([wg(g_z, seq.view(B, S * H)[:, :H] if st.lay is None else st.cls_seq,
+                          self._grad(m.bert.pooler.dense.weight), self._grad(m.bert.pooler.dense.bias))], B)
+            g16.index_add_(0, st.cls_rows, ops.linear(g_z, self.head_t["pool"]))
         elif not acc:
-            for prm in (m.next_action.linear.weight, m.next_action.linear.bias, m.bert.pooler.dense.weight,
-                        m.bert.pooler.dense.bias):
-                self._grad(prm).zero_()
-        if comm is not None:
-            # data-parallel: the head / pooler gradients are final here, before the encoder backward has started -- their
-            # all-reduce goes out first and hides under the whole backward (round 3 reduced them last, with the embeddings)
-            rng = self._param_ranges(self._head_params())
-            comm["launch"](rng)
-            comm["done"].extend(rng)
-        self._trunk_bwd(st, None, acc, comm, word_grad_ready=True)
-        return (loss, mask_loss, next_loss, token_loss, words_acc, action_acc, token_acc)
+            self._zero_head_grads("action", "pooler")
 
     def _head_params(self):
         """The head / pooler parameters whose gradients are final before the encoder backward starts."""
-        m = self.model
-        pr, lin_tok = m.mlmhead.predictions, m.token_head[0]
-        tied = pr.decoder.weight is m.bert.embeddings.word_embeddings.weight
-        return [pr.transform.dense.weight, pr.transform.dense.bias, pr.transform.LayerNorm.weight,
-                pr.transform.LayerNorm.bias, pr.bias, lin_tok.weight, lin_tok.bias,
-                m.next_action.linear.weight, m.next_action.linear.bias, m.bert.pooler.dense.weight,
-                m.bert.pooler.dense.bias] + ([] if tied else [pr.decoder.weight])
+        return self._head_group(*_HEAD_GROUPS)
 
     def _param_ranges(self, params):
         """Slab ranges [start, end) of the given parameters, ends rounded up to the alignment granule (the padding belongs
@@ -829,6 +926,12 @@ class PretrainEngine(object):
                 out.append((s_, e_))
         return out
 
+    def _layer_chunk_ranges(self, lo, hi):
+        """The decay and the no-decay slab range of layers [lo, hi), ends rounded up to the slab's alignment granule (the
+        padding belongs to no parameter)."""
+        return [(self.layer_ranges[lo][k][0], min(round_up(self.layer_ranges[hi - 1][k][1], ALIGN), self.flat.total))
+                for k in (0, 1)]
+
     def _trunk_bwd(self, st, g32, acc, comm=None, word_grad_ready=False, d_hidden=None):
         """Back through the trunk: g32 fp32 [rows, H] = dL/d(sequence output) in the layout of the forward (st), or None
         when the caller has already put it (bf16) into bufs.g; the gradients of the encoder layers, the embeddings and the
@@ -836,11 +939,10 @@ class PretrainEngine(object):
         if st.serial != self._fwd_serial:
             raise RuntimeError("the activations of this forward were overwritten by a later forward of the same engine; "
                                "run backward before the next forward")
-        m, cfg, f, emb, bufs = self.model, self.cfg, self.flat, st.emb, st.bufs
-        B, T, R, S, H, I, nh, L, Mr, lay = st.B, st.T, st.R, st.S, st.H, st.I, st.nh, st.L, st.Mr, st.lay
-        hs, x_enc, enc_mask, mask_additive, dp_kw = st.hs, st.x_enc, st.enc_mask, st.mask_additive, st.dp_kw
-        p_h, p_a, seed, ids, tt, pos_ids, eps = st.p_h, st.p_a, st.seed, st.ids, st.tt, st.pos_ids, st.eps
-        img, img_pre, a_img, batch = st.img, st.img_pre if st.img is not None else None, st.a_img, st.batch
+        m, bufs = self.model, st.bufs
+        emb = m.bert.embeddings
+        B, T, R, S, H, L, Mr, lay = st.B, st.T, st.R, st.S, st.H, st.L, st.Mr, st.lay
+        p_h, seed, ids, tt, pos_ids, img = st.p_h, st.seed, st.ids, st.tt, st.pos_ids, st.img
         word_grad = self._grad(emb.word_embeddings.weight)
         if not acc and not word_grad_ready:
             word_grad.zero_()
@@ -850,54 +952,31 @@ class PretrainEngine(object):
         bufs.fit_dq32()   # (the deterministic switch is read here, per backward: no copy of it is kept)
         if d_hidden is not None and comm is not None:
             raise NotImplementedError("gradients of intermediate hidden states together with the chunked data-parallel backward")
-        if st.hist is not None:
-            if comm is not None:
-                raise NotImplementedError("encoder_history_states together with the chunked data-parallel backward is not served")
-            self._encoder_backward_unrolled(bufs, x_enc, enc_mask, g, B, S, acc, p_h, p_a, seed, lay, mask_additive, hs,
-                                            inject=d_hidden, hist=st.hist)
-        elif ops.profiling() or hs is not None:
-            self._encoder_backward_unrolled(bufs, x_enc, enc_mask, g, B, S, acc, p_h, p_a, seed, lay, mask_additive, hs,
-                                            inject=d_hidden)
-        elif d_hidden is not None:
-            # a caller's gradients with respect to intermediate hidden states (output_hidden_states in trunk-level training,
-            # oscar/modeling_bert.py:146-158): the C loop one layer at a time, d_hidden[l + 1] (the output of layer l; bf16
-            # rows in the forward's layout) added to the running gradient in front of layer l's backward, d_hidden[0] (the
-            # embedding output) behind layer 0's.  (d_hidden[L] is part of g already.)
-            for lo in range(L - 1, -1, -1):
-                if lo + 1 < L and d_hidden[lo + 1] is not None:
-                    g.add_(d_hidden[lo + 1])
-                sub = lambda arr, typ: (typ * 1).from_address(ctypes.addressof(arr) + lo * ctypes.sizeof(typ))
-                x_in = x_enc if lo == 0 else bufs.layers[lo - 1]["out"]
-                ops.encoder_backward(sub(self.w_tab, _lib.LayerWeights), sub(self.wt_tab, _lib.LayerWeightsT),
-                                     sub(bufs.acts, _lib.LayerActs), sub(self.g_tab, _lib.LayerGrads), x_in, enc_mask, mask_additive,
-                                     g, bufs.ws, B, S, H, nh, I, cfg.layer_norm_eps, accumulate=acc, layer0=lo, seq=lay,
-                                     **dp_kw, **self._overlap_kw(bufs))
-            if d_hidden[0] is not None:
-                g.add_(d_hidden[0])
-        elif comm is None:
-            ops.encoder_backward(self.w_tab, self.wt_tab, bufs.acts, self.g_tab, x_enc, enc_mask, mask_additive, g, bufs.ws, B, S,
-                                 H, nh, I, cfg.layer_norm_eps, accumulate=acc, seq=lay, **dp_kw, **self._overlap_kw(bufs))
+        if st.hist is not None and comm is not None:
+            raise NotImplementedError("encoder_history_states together with the chunked data-parallel backward is not served")
+        if st.hist is not None or ops.profiling() or st.hs is not None:
+            self._encoder_backward_unrolled(bufs, st.x_enc, st.enc_mask, g, B, S, acc, p_h, st.p_a, seed, lay, st.mask_additive,
+                                            st.hs, inject=d_hidden, hist=st.hist)
         else:
-            # data-parallel: backward in layer chunks (last layers first); as soon as a chunk's kernels are
-            # enqueued its gradient ranges are all-reduced on the communicator's stream, under the backward
-            # of the earlier layers
-            step = max(1, int(comm["layers_per_chunk"]))
-            hi = L
-            while hi > 0:
+            # The C loop, last layers first: all layers in one call, or
+            #  * data-parallel (comm): in chunks of layers -- as soon as a chunk's kernels are enqueued its gradient ranges are
+            #    all-reduced on the communicator's stream, under the backward of the earlier layers;
+            #  * a caller's gradients with respect to intermediate hidden states (output_hidden_states in trunk-level training,
+            #    oscar/modeling_bert.py:146-158): one layer at a time, d_hidden[l + 1] (the output of layer l; bf16 rows in the
+            #    forward's layout) added to the running gradient in front of layer l's backward, d_hidden[0] (the embedding
+            #    output) behind layer 0's.  (d_hidden[L] is part of g already.)
+            step = 1 if d_hidden is not None else max(1, L if comm is None else int(comm["layers_per_chunk"]))
+            for hi in range(L, 0, -step):
                 lo = max(0, hi - step)
-                n = hi - lo
-                sub = lambda arr, typ: (typ * n).from_address(ctypes.addressof(arr) + lo * ctypes.sizeof(typ))
-                x_in = x_enc if lo == 0 else bufs.layers[lo - 1]["out"]
-                ops.encoder_backward(sub(self.w_tab, _lib.LayerWeights), sub(self.wt_tab, _lib.LayerWeightsT),
-                                     sub(bufs.acts, _lib.LayerActs), sub(self.g_tab, _lib.LayerGrads), x_in, enc_mask, mask_additive,
-                                     g, bufs.ws, B, S, H, nh, I, cfg.layer_norm_eps, accumulate=acc, layer0=lo, seq=lay,
-                                     **dp_kw, **self._overlap_kw(bufs))
-                # (range ends rounded up to the slab's alignment granule: the padding belongs to no parameter)
-                rng = [(self.layer_ranges[lo][k][0], min(round_up(self.layer_ranges[hi - 1][k][1], ALIGN), f.total))
-                       for k in (0, 1)]
-                comm["launch"](rng)
-                comm["done"].extend(rng)
-                hi = lo
+                if d_hidden is not None and hi < L and d_hidden[hi] is not None:
+                    g.add_(d_hidden[hi])
+                self._encoder_backward_layers(st, g, acc, lo, hi)
+                if comm is not None:
+                    rng = self._layer_chunk_ranges(lo, hi)
+                    comm["launch"](rng)
+                    comm["done"].extend(rng)
+            if d_hidden is not None and d_hidden[0] is not None:
+                g.add_(d_hidden[0])
         if lay is not None:   # dL/dx0 back in the padded row order (zero at the padding rows, as in the padded run)
             # gathers: padded row -> its compact row, or the zero row kept behind the compact rows (Mr < M here); the text
             # and the region positions land in two contiguous blocks (what the embedding and the region backward read)
@@ -911,7 +990,8 @@ class PretrainEngine(object):
         # embeddings: text rows
         de = ops.embed_layernorm_bwd(ids, tt, pos_ids, emb.word_embeddings.weight.detach(),
                                      emb.position_embeddings.weight.detach(), emb.token_type_embeddings.weight.detach(),
-                                     emb.LayerNorm.weight.detach(), eps, g_text, g_pitch, self._grad(emb.LayerNorm.weight),
+                                     emb.LayerNorm.weight.detach(), emb.LayerNorm.variance_epsilon, g_text, g_pitch,
+                                     self._grad(emb.LayerNorm.weight),
                                      self._grad(emb.LayerNorm.bias), ws=bufs.ws_t["ln_partial"], accumulate=acc,
                                      drop=(p_h, seed, ops.SITE_EMB))
         pos_grad, type_grad = self._grad(emb.position_embeddings.weight), self._grad(emb.token_type_embeddings.weight)
@@ -936,19 +1016,27 @@ class PretrainEngine(object):
             g_img = g_reg if g_reg is not None else g.view(B, S, H)[:, T:].reshape(B * R, H)
             if p_h > 0.0:
                 ops.apply_dropout(g_img, (p_h, seed, ops.SITE_IMG))   # g is not read again after this point
-            if img_pre is not None:   # back through the image LayerNorm
+            if st.img_pre is not None:   # back through the image LayerNorm
                 ln = m.bert.LayerNorm
-                g_img = ops.layernorm_bwd(img_pre, g_img.contiguous(), ln.weight.detach(), ln.variance_epsilon,
+                g_img = ops.layernorm_bwd(st.img_pre, g_img.contiguous(), ln.weight.detach(), ln.variance_epsilon,
                                           self._grad(ln.weight), self._grad(ln.bias), ws=bufs.ws_t["ln_partial"],
                                           accumulate=acc)
-            ops.wgrad([dict(dy=g_img, x=a_img, dw=self.dw_img, db=self.db_img)], B * R)
-            D = m.bert.img_dim
-            gi, gl = self._grad(m.bert.img_embedding.weight), self._grad(m.bert.location_embeds.weight)
-            gbi, gbl = self._grad(m.bert.img_embedding.bias), self._grad(m.bert.location_embeds.bias)
-            if acc:
-                gi.add_(self.dw_img[:, :D]); gl.add_(self.dw_img[:, D:D + 128]); gbi.add_(self.db_img); gbl.add_(self.db_img)
-            else:
-                gi.copy_(self.dw_img[:, :D]); gl.copy_(self.dw_img[:, D:D + 128]); gbi.copy_(self.db_img); gbl.copy_(self.db_img)
+            ops.wgrad([dict(dy=g_img, x=st.a_img, dw=self.dw_img, db=self.db_img)], B * R)
+            D, bt = m.bert.img_dim, m.bert   # (the K-concatenated operand's columns are the two weights' gradients)
+            for prm, src in ((bt.img_embedding.weight, self.dw_img[:, :D]), (bt.location_embeds.weight, self.dw_img[:, D:D + 128]),
+                             (bt.img_embedding.bias, self.db_img), (bt.location_embeds.bias, self.db_img)):
+                getattr(self._grad(prm), "add_" if acc else "copy_")(src)
+
+    def _encoder_backward_layers(self, st, g, acc, lo, hi):
+        """Layers [lo, hi) of the forward `st` through the C loop (one library call), last layer first: g, the running
+        gradient, enters as dL/d(output of layer hi - 1) and leaves as dL/d(input of layer lo)."""
+        bufs = st.bufs
+        sub = lambda arr, typ: (typ * (hi - lo)).from_address(ctypes.addressof(arr) + lo * ctypes.sizeof(typ))
+        ops.encoder_backward(sub(self.w_tab, _lib.LayerWeights), sub(self.wt_tab, _lib.LayerWeightsT),
+                             sub(bufs.acts, _lib.LayerActs), sub(self.g_tab, _lib.LayerGrads),
+                             st.x_enc if lo == 0 else bufs.layers[lo - 1]["out"], st.enc_mask, st.mask_additive, g, bufs.ws,
+                             st.B, st.S, st.H, st.nh, st.I, self.cfg.layer_norm_eps, accumulate=acc, p_hidden=st.p_h,
+                             p_attn=st.p_a, drop_seed=st.seed, layer0=lo, seq=st.lay, **self._overlap_kw(bufs))
 
     # ------------------------------------------------------------------------------ trunk-level training
     def trunk_forward(self, batch, head_mask=None, training=None, unmasked_only=False, want_hidden=False, want_attn=False,
@@ -970,26 +1058,23 @@ class PretrainEngine(object):
                                           "want_hidden and want_attn")
             st = training_f32.trunk_forward(self, batch, head_mask, bool(training))
             return st.seq.view(st.B, st.S, st.H).clone(), st.pooled.clone(), st
-        if history:
-            st = self._trunk_fwd(batch, head_mask, None, None, bool(training), bool(unmasked_only), history=history)
-        else:
-            st = self._trunk_fwd(batch, head_mask, None, None, bool(training), bool(unmasked_only))
-        st.d_history = None
-        # the caller's hidden states come from the fp16 copy of the last LayerNorm's output where the layer keeps one (the
-        # bf16 copy is the heads' / pooler's GEMM operand)
+        st = self._trunk_fwd(batch, head_mask, None, None, bool(training), bool(unmasked_only), history=history)
         n = st.seq.shape[0]
-        if st.bufs.ln_h is not None:
-            last = st.bufs.ln_h[1][:n].float()
-        elif st.bufs.ln_residual:
-            # LN_RESIDUAL (the default): no fp16 copy of a LayerNorm output exists -- the last layer's is rebuilt at fp32 from
-            # its fp16 input and the row statistics its kernel wrote, as the residual adds do (one elementwise pass; the bf16
-            # output stays the heads' / pooler's GEMM operand).  8 more significant bits than the bf16 rows.
-            d = st.bufs.layers[-1]
-            ln = self.model.bert.encoder.layer[-1].output.LayerNorm
-            last = ((d["out_pre"][:n].float() - d["ln2_mean"][:n, None]) * d["ln2_rstd"][:n, None] * ln.weight.detach().float()
+
+        def out32(l):
+            """Layer l's output rows at fp32, from the best copy kept: the fp16 copy of the last LayerNorm's output where the
+            layers keep one; under LN_RESIDUAL (the default) rebuilt from the LayerNorm's fp16 input and the row statistics
+            its kernel wrote, as the residual adds do (8 more significant bits than the bf16 rows, which stay the heads' /
+            pooler's GEMM operand); the bf16 rows otherwise."""
+            d = st.bufs.layers[l]
+            if st.bufs.ln_h is not None and l == st.L - 1:
+                return st.bufs.ln_h[1][:n].float()
+            if not st.bufs.ln_residual:
+                return d["out"][:n].float()
+            ln = self.model.bert.encoder.layer[l].output.LayerNorm
+            return ((d["out_pre"][:n].float() - d["ln2_mean"][:n, None]) * d["ln2_rstd"][:n, None] * ln.weight.detach().float()
                     + ln.bias.detach().float())
-        else:
-            last = st.seq.float()
+
         def padded(rows32):
             if st.lay is None:
                 return rows32.view(st.B, st.S, st.H)
@@ -997,7 +1082,7 @@ class PretrainEngine(object):
             out.index_copy_(0, st.lay.index, rows32)
             return out.view(st.B, st.S, st.H)
 
-        seq = padded(last)
+        seq = padded(out32(st.L - 1))
         attn = None
         if want_attn:
             # all_attentions (oscar/modeling_bert.py:62-79, 160-167): per layer the probabilities AFTER dropout and head_mask,
@@ -1023,16 +1108,8 @@ class PretrainEngine(object):
                 attn.append(pr)
         if not want_hidden:
             return (seq, st.pooled.clone(), st) + ((None, attn) if want_attn else ())
-        # all_hidden_states (oscar/modeling_bert.py:146-158): the embedding output, then every layer's output -- fp32, rebuilt
-        # from the fp16 sums and the row statistics where the layer keeps no higher-precision copy (as `last` above)
-        hidden = [padded(st.x_enc[:n].float())]
-        for l, d in enumerate(st.bufs.layers[:-1]):
-            if st.bufs.ln_residual:
-                ln = self.model.bert.encoder.layer[l].output.LayerNorm
-                hidden.append(padded((d["out_pre"][:n].float() - d["ln2_mean"][:n, None]) * d["ln2_rstd"][:n, None]
-                                     * ln.weight.detach().float() + ln.bias.detach().float()))
-            else:
-                hidden.append(padded(d["out"][:n].float()))
+        # all_hidden_states (oscar/modeling_bert.py:146-158): the embedding output, then every layer's output
+        hidden = [padded(st.x_enc[:n].float())] + [padded(out32(l)) for l in range(st.L - 1)]
         hidden.append(seq.clone())
         return (seq, st.pooled.clone(), st, hidden) + ((attn,) if want_attn else ())
 
@@ -1063,7 +1140,7 @@ class PretrainEngine(object):
             if d_hidden is not None:
                 raise NotImplementedError("PretrainEngine(precision='fp32') serves trunk_backward without d_hidden")
             return self._trunk_backward_f32(st, d_seq, d_pooled, bool(accumulate))
-        m, bufs, acc = self.model, st.bufs, bool(accumulate)
+        bufs, acc = st.bufs, bool(accumulate)
         B, S, H, M, Mr, lay = st.B, st.S, st.H, st.M, st.Mr, st.lay
         g32 = bufs.g_seq32[:Mr]
         rows = lambda t: (t.detach().reshape(M, H).float() if lay is None
@@ -1081,35 +1158,27 @@ class PretrainEngine(object):
             g32.copy_(d_seq.detach().reshape(M, H))
         else:
             torch.index_select(d_seq.detach().reshape(M, H).float(), 0, lay.index, out=g32)
-        pw, pb = m.bert.pooler.dense.weight, m.bert.pooler.dense.bias
+        pw, pb = self._head_group("pooler")
         if d_pooled is not None:
             g_z = (d_pooled.detach().float() * (1.0 - st.pooled * st.pooled)).to(BF16)
             x_cls = st.seq.view(B, S * H)[:, :H] if lay is None else st.cls_seq
             ops.wgrad([dict(dy=g_z, x=x_cls, dw=self._grad(pw), db=self._grad(pb), accumulate=acc)], B)
             g32.index_add_(0, st.cls_rows, ops.linear(g_z, self.head_t["pool"]).float())
         elif not acc:
-            self._grad(pw).zero_()
-            self._grad(pb).zero_()
+            self._zero_head_grads("pooler")
         self._trunk_bwd(st, g32, acc, d_hidden=extra)
         if st.hist is not None:
             st.d_history = list(st.hist["d"])
         if st.img is None and not acc:
-            for prm in (m.bert.img_embedding.weight, m.bert.img_embedding.bias, m.bert.location_embeds.weight,
-                        m.bert.location_embeds.bias):
-                self._grad(prm).zero_()
-            if getattr(m.bert, "use_img_layernorm", None):
-                self._grad(m.bert.LayerNorm.weight).zero_()
-                self._grad(m.bert.LayerNorm.bias).zero_()
+            self._zero_head_grads("region")
 
     def _trunk_backward_f32(self, st, d_seq, d_pooled, acc):
-        m = self.model
         g = (torch.zeros((st.M, st.H), dtype=torch.float32, device=st.dev) if d_seq is None
              else d_seq.detach().reshape(st.M, st.H).float().clone())
         if d_pooled is not None:
             training_f32.pooler_backward(self, st, g, d_pooled.detach().float(), acc)
         elif not acc:
-            self._grad(m.bert.pooler.dense.weight).zero_()
-            self._grad(m.bert.pooler.dense.bias).zero_()
+            self._zero_head_grads("pooler")
         training_f32.trunk_backward(self, st, g, acc)
 
     # ---- the launch sequences of vt_encoder_forward/backward_bf16 issued op by op (bench.py's per-kernel timing)
@@ -1122,55 +1191,42 @@ class PretrainEngine(object):
         nh, eps = cfg.num_attention_heads, cfg.layer_norm_eps
         cur, cur_h, cur_ln = x0, None, None
         n = x0.shape[0]
-        for l, ((t, _), a) in enumerate(zip(self._keep, bufs.layers)):
+        for l, ((t, _, _), a) in enumerate(zip(self._layers, bufs.layers)):
             a = {k: (v if k in ("lse", "keep_bits") else v[:n]) for k, v in a.items()}   # the rows in use (all, or the compacted ones)
-            kb = a.get("keep_bits") if p_a > 0.0 else None
+            # head_mask (oscar/modeling_bert.py:65-66): the attention kernel's own context is kept for the backward (ctx_raw),
+            # its per-head scaled copy is what the output projection sees
+            raw = a["ctx"] if hs is None else bufs.ctx_raw(l)[:n]
             if hist is None:
                 ops.linear(cur, t["w_qkv"], t["b_qkv"], out=a["qkv"])
-            if hist is not None:
+                ops.attention_fwd(a["qkv"], B, S, nh, mask=mask, mask_additive=mask_additive, out=raw, lse=a["lse"],
+                                  drop=(p_a, seed, ops.site_attn(l)), seq=lay, keep_bits=a.get("keep_bits") if p_a > 0.0 else None)
+            else:
                 St, H = hist["Sh"] + S, cur.shape[1]
                 xs = torch.cat([hist["src"][l], cur.view(B, S, H)], 1).reshape(B * St, H)
                 qkv = ops.linear(xs, t["w_qkv"], t["b_qkv"])
                 kbr = torch.empty(ops.keep_words_rect(B, nh, S, St), dtype=torch.int32, device=cur.device) if p_a > 0.0 else None
                 hist["xs"][l], hist["qkv"][l], hist["keep"][l] = xs, qkv, kbr
-                # (head_mask: the kernel's own context is kept for the backward, its scaled copy feeds the output projection)
-                raw = a["ctx"] if hs is None else bufs.ctx_raw(l)[:n]
                 ops.attention_rect_fwd(qkv, B, S, St, nh, mask=mask, mask_additive=mask_additive, out=raw, lse=a["lse"],
                                        drop=(p_a, seed, ops.site_attn(l)), keep_bits=kbr)
-                if hs is not None:
-                    ops.scale_heads(raw, hs[l].contiguous(), out=a["ctx"])
-            elif hs is None:
-                ops.attention_fwd(a["qkv"], B, S, nh, mask=mask, mask_additive=mask_additive, out=a["ctx"], lse=a["lse"],
-                                  drop=(p_a, seed, ops.site_attn(l)), seq=lay, keep_bits=kb)
-            else:
-                # head_mask (oscar/modeling_bert.py:65-66): the attention kernel's own context is kept for the backward
-                # (ctx_raw), its per-head scaled copy is what the output projection sees
-                raw = bufs.ctx_raw(l)[:n]
-                ops.attention_fwd(a["qkv"], B, S, nh, mask=mask, mask_additive=mask_additive, out=raw, lse=a["lse"],
-                                  drop=(p_a, seed, ops.site_attn(l)), seq=lay, keep_bits=kb)
+            if hs is not None:
                 ops.scale_heads(raw, hs[l].contiguous(), out=a["ctx"])
-            # (fp16 copies of the stream, ops.F16_STREAM: attn_pre / out_pre are fp16 tensors, the residual adds read the
-            # LayerNorm outputs' fp16 copies ln1_h / ln2_h -- the library learns all of it from the dtypes)
-            if bufs.ln_residual:
-                # (ops.LN_RESIDUAL: no fp16 copies -- each residual add rebuilds the previous LayerNorm from its fp16 input
-                # and the statistics its kernel wrote; the same arithmetic as the C loop's ln_residual_mode 1)
-                ops.linear(a["ctx"], t["w_ao"], t["b_ao"], residual=cur if cur_h is None else cur_h, out=a["attn_pre"],
-                           drop=(p_h, seed, ops.site_selfout(l)), residual_ln=cur_ln)
-                ops.layernorm(a["attn_pre"], t["ln1_g"], t["ln1_b"], eps, out=a["attn_out"], mean=a["ln1_mean"], rstd=a["ln1_rstd"])
-                ops.linear(a["attn_out"], t["w_in"], t["b_in"], act=ACT_GELU, out=a["mid"], pre_act_out=a["mid_pre"])
-                ops.linear(a["mid"], t["w_out"], t["b_out"], residual=a["attn_pre"], out=a["out_pre"],
-                           drop=(p_h, seed, ops.site_out(l)), residual_ln=(a["ln1_mean"], a["ln1_rstd"], t["ln1_g"], t["ln1_b"]))
-                ops.layernorm(a["out_pre"], t["ln2_g"], t["ln2_b"], eps, out=a["out"], mean=a["ln2_mean"], rstd=a["ln2_rstd"])
-                cur, cur_h, cur_ln = a["out"], a["out_pre"], (a["ln2_mean"], a["ln2_rstd"], t["ln2_g"], t["ln2_b"])
-                continue
+            # the residual stream (ops.F16_STREAM: attn_pre / out_pre are fp16 sums -- the library learns it from the dtypes): a
+            # residual add reads the fp16 copy ln1_h / ln2_h of the LayerNorm output where the layer keeps one, or rebuilds the
+            # LayerNorm from its fp16 input and the statistics its kernel wrote (ops.LN_RESIDUAL; the same arithmetic as the C
+            # loop's ln_residual_mode 1)
+            res = bufs.ln_residual
             ops.linear(a["ctx"], t["w_ao"], t["b_ao"], residual=cur if cur_h is None else cur_h, out=a["attn_pre"],
-                       drop=(p_h, seed, ops.site_selfout(l)))
-            ops.layernorm(a["attn_pre"], t["ln1_g"], t["ln1_b"], eps, out=a["attn_out"], out_h=a.get("ln1_h"))
+                       drop=(p_h, seed, ops.site_selfout(l)), residual_ln=cur_ln)
+            ops.layernorm(a["attn_pre"], t["ln1_g"], t["ln1_b"], eps, out=a["attn_out"], mean=a.get("ln1_mean"),
+                          rstd=a.get("ln1_rstd"), out_h=a.get("ln1_h"))
             ops.linear(a["attn_out"], t["w_in"], t["b_in"], act=ACT_GELU, out=a["mid"], pre_act_out=a["mid_pre"])
-            ops.linear(a["mid"], t["w_out"], t["b_out"], residual=a.get("ln1_h", a["attn_out"]), out=a["out_pre"],
-                       drop=(p_h, seed, ops.site_out(l)))
-            ops.layernorm(a["out_pre"], t["ln2_g"], t["ln2_b"], eps, out=a["out"], out_h=a.get("ln2_h"))
-            cur, cur_h = a["out"], a.get("ln2_h")
+            ops.linear(a["mid"], t["w_out"], t["b_out"], residual=a["attn_pre"] if res else a.get("ln1_h", a["attn_out"]),
+                       out=a["out_pre"], drop=(p_h, seed, ops.site_out(l)),
+                       residual_ln=(a["ln1_mean"], a["ln1_rstd"], t["ln1_g"], t["ln1_b"]) if res else None)
+            ops.layernorm(a["out_pre"], t["ln2_g"], t["ln2_b"], eps, out=a["out"], mean=a.get("ln2_mean"),
+                          rstd=a.get("ln2_rstd"), out_h=a.get("ln2_h"))
+            cur, cur_h = a["out"], a["out_pre"] if res else a.get("ln2_h")
+            cur_ln = (a["ln2_mean"], a["ln2_rstd"], t["ln2_g"], t["ln2_b"]) if res else None
 
     def _overlap_kw(self, bufs):
         """Second workspace set + side stream for the wgrad / dgrad overlap (off: overlap_wgrad = False)."""
@@ -1189,26 +1245,28 @@ class PretrainEngine(object):
         weights see the hidden rows only; key and value biases apply to history rows as in the reference)."""
         cfg = self.cfg
         nh, eps, M = cfg.num_attention_heads, cfg.layer_norm_eps, x0.shape[0]
-        rowed = ("g_pre", "g_pre2", "g_mid", "g_ctx", "g_qkv", "g_pre_d", "g_pre2_d")
-        w = {k: (v[:M] if k in rowed else v) for k, v in bufs.ws_t.items()}
+        w = {k: (v[:M] if k in bufs.ws_rowed else v) for k, v in bufs.ws_t.items()}
         for l in range(cfg.num_hidden_layers - 1, -1, -1):
             if inject is not None and l + 1 < cfg.num_hidden_layers and inject[l + 1] is not None:
                 g.add_(inject[l + 1])   # dL/d(output of layer l) from a caller that read the intermediate hidden states
-            (t, gr), a, (_, wt) = self._keep[l], bufs.layers[l], self.wt[l]
+            (t, gr, wt), a = self._layers[l], bufs.layers[l]
             a = {k: (v if k in ("lse", "keep_bits") else v[:M]) for k, v in a.items()}
             x_in = x0 if l == 0 else bufs.layers[l - 1]["out"][:M]
             hd = p_h > 0.0   # with hidden dropout the dense outputs' gradients are the masked copies
             g_pre_dn, g_pre2_dn = (w["g_pre_d"], w["g_pre2_d"]) if hd else (w["g_pre"], w["g_pre2"])
-            ops.layernorm_bwd(a["out_pre"], g, t["ln2_g"], eps, gr["d_ln2_g"], gr["d_ln2_b"], dx=w["g_pre"],
+            ops.layernorm_bwd(a["out_pre"], g, t["ln2_g"], eps, gr["ln2_g"], gr["ln2_b"], dx=w["g_pre"],
                               ws=w["ln_partial"], accumulate=acc, dx_dropped=w["g_pre_d"] if hd else None,
                               drop=(p_h, seed, ops.site_out(l)))
             ops.linear(g_pre_dn, wt["wt_out"], residual=a["mid_pre"], act=ACT_MUL, out=w["g_mid"])
             ops.linear(w["g_mid"], wt["wt_in"], residual=w["g_pre"], out=g)
-            ops.layernorm_bwd(a["attn_pre"], g, t["ln1_g"], eps, gr["d_ln1_g"], gr["d_ln1_b"], dx=w["g_pre2"],
+            ops.layernorm_bwd(a["attn_pre"], g, t["ln1_g"], eps, gr["ln1_g"], gr["ln1_b"], dx=w["g_pre2"],
                               ws=w["ln_partial"], accumulate=acc, dx_dropped=w["g_pre2_d"] if hd else None,
                               drop=(p_h, seed, ops.site_selfout(l)))
             ops.linear(g_pre2_dn, wt["wt_ao"], out=w["g_ctx"])
             g_ctx, ctx_l = w["g_ctx"], a["ctx"]
+            # the layer's weight-gradient problems (the packed projection's joins them below)
+            prob = lambda dy, x, k: dict(dy=dy, x=x, dw=gr["w_" + k], db=gr["b_" + k], accumulate=acc)
+            ffn, ao = [prob(w["g_mid"], a["attn_out"], "in"), prob(g_pre_dn, a["mid"], "out")], prob(g_pre2_dn, a["ctx"], "ao")
             if hs is not None:   # back through the head scaling: dL/d(raw context) = head_mask * dL/d(scaled context)
                 g_ctx = ops.scale_heads(w["g_ctx"], hs[l].contiguous())
                 ctx_l = bufs.ctx_raw(l)[:M]
@@ -1222,19 +1280,14 @@ class PretrainEngine(object):
                 g.copy_((gx[:, Sh:] + w["g_pre2"].view(B, S, H).float()).reshape(M, H))
                 if hist["need"][l]:
                     hist["d"][l] = gx[:, :Sh].clone()
-                ops.wgrad([dict(dy=g_ext, x=hist["xs"][l], dw=gr["d_w_qkv"], db=gr["d_b_qkv"], accumulate=acc)], B * St)
-                ops.wgrad([dict(dy=w["g_mid"], x=a["attn_out"], dw=gr["d_w_in"], db=gr["d_b_in"], accumulate=acc),
-                           dict(dy=g_pre_dn, x=a["mid"], dw=gr["d_w_out"], db=gr["d_b_out"], accumulate=acc),
-                           dict(dy=g_pre2_dn, x=a["ctx"], dw=gr["d_w_ao"], db=gr["d_b_ao"], accumulate=acc)], M)
+                ops.wgrad([prob(g_ext, hist["xs"][l], "qkv")], B * St)
+                ops.wgrad(ffn + [ao], M)
                 continue
             ops.attention_bwd(a["qkv"], g_ctx, ctx_l, a["lse"], B, S, nh, mask=mask, mask_additive=mask_additive,
                               out=w["g_qkv"], delta_ws=w["delta"], dq32_ws=w.get("dq32"), drop=(p_a, seed, ops.site_attn(l)),
                               seq=lay, keep_bits=a.get("keep_bits") if p_a > 0.0 else None)
             ops.linear(w["g_qkv"], wt["wt_qkv"], residual=w["g_pre2"], out=g)
-            ops.wgrad([dict(dy=w["g_mid"], x=a["attn_out"], dw=gr["d_w_in"], db=gr["d_b_in"], accumulate=acc),
-                       dict(dy=g_pre_dn, x=a["mid"], dw=gr["d_w_out"], db=gr["d_b_out"], accumulate=acc),
-                       dict(dy=w["g_qkv"], x=x_in, dw=gr["d_w_qkv"], db=gr["d_b_qkv"], accumulate=acc),
-                       dict(dy=g_pre2_dn, x=a["ctx"], dw=gr["d_w_ao"], db=gr["d_b_ao"], accumulate=acc)], M)
+            ops.wgrad(ffn + [prob(w["g_qkv"], x_in, "qkv"), ao], M)
         if inject is not None and inject[0] is not None:
             g.add_(inject[0])           # ... and with respect to the embedding output
 
@@ -1302,8 +1355,6 @@ class PretrainEngine(object):
         heads are not persistent).  A layer's weights are not read again once its backward is enqueued (dgrad reads the
         transposed copies, rebuilt at the start of the next step); embeddings, region projection and everything else follow
         on the main stream, which then waits for the side stream."""
-        from .distributed import complement_ranges
-
         if self._adam_stream is None:
             self._adam_stream = torch.cuda.Stream(device=self.flat.p.device)
         side = self._adam_stream
@@ -1322,7 +1373,7 @@ class PretrainEngine(object):
             self.step_count -= 1   # no update was completed on behalf of this step's counter
             torch.cuda.current_stream().wait_stream(side)
             raise
-        self._adam_ranges(consts, complement_ranges(self.flat.total, comm["done"]), 1.0)
+        self._adam_ranges(consts, distributed.complement_ranges(self.flat.total, comm["done"]), 1.0)
         torch.cuda.current_stream().wait_stream(side)
         self._adam_end()
         return out
@@ -1331,35 +1382,25 @@ class PretrainEngine(object):
     def shard_atoms(self):
         """The ranges forward_backward hands to comm["launch"] with one layer per chunk, in slab order: the heads' ranges,
         every layer's decay and no-decay range (ends rounded up to ALIGN, as _trunk_bwd rounds them), and what is left."""
-        from .distributed import complement_ranges
-
-        f = self.flat
-        heads = self._param_ranges(self._head_params()) if self.has_heads else []
-        layers = [(lr_[k][0], min(round_up(lr_[k][1], ALIGN), f.total)) for lr_ in self.layer_ranges for k in (0, 1)]
-        return sorted(heads + layers + complement_ranges(f.total, heads + layers))
+        done = self._param_ranges(self._head_params()) if self.has_heads else []
+        done = done + [r_ for l in range(len(self.layer_ranges)) for r_ in self._layer_chunk_ranges(l, l + 1)]
+        return sorted(done + distributed.complement_ranges(self.flat.total, done))
 
     def shard_launch_ranges(self):
         """The launches of one overlapped step with one layer per chunk, in launch order: heads, layers last first, tail."""
-        from .distributed import complement_ranges
-
-        f = self.flat
         heads = self._param_ranges(self._head_params()) if self.has_heads else []
-        layers = [[(lr_[k][0], min(round_up(lr_[k][1], ALIGN), f.total)) for k in (0, 1)] for lr_ in reversed(self.layer_ranges)]
+        layers = [self._layer_chunk_ranges(l, l + 1) for l in reversed(range(len(self.layer_ranges)))]
         done = heads + [r_ for l_ in layers for r_ in l_]
-        return [r_ for r_ in [heads] + layers + [complement_ranges(f.total, done)] if r_]
+        return [r_ for r_ in [heads] + layers + [distributed.complement_ranges(self.flat.total, done)] if r_]
 
     def mirror_only_names(self):
         """The slab entries the step reads ONLY through the bf16 mirror: what the layer tables point at in flat.mirror and
         what the heads, the pooler and the region projection take via _mirror(...) -- minus every entry that some kernel
         also takes as the fp32 parameter itself (the three embedding tables; the tied MLM decoder IS the word table)."""
-        m = self.model
-        via_mirror = [m.bert.pooler.dense.weight, m.bert.img_embedding.weight, m.bert.location_embeds.weight]
-        if self.has_heads:
-            via_mirror += [m.mlmhead.predictions.transform.dense.weight, m.mlmhead.predictions.decoder.weight,
-                           m.token_head[0].weight, m.next_action.linear.weight]
-        emb = m.bert.embeddings
+        emb = self.model.bert.embeddings
         as_fp32 = [emb.word_embeddings.weight, emb.position_embeddings.weight, emb.token_type_embeddings.weight]
-        names = set(self._mirror_views) | {self._name_of(p_) for p_ in via_mirror}
+        names = {"bert.encoder.layer.%d.%s" % (l, n) for l in range(self.cfg.num_hidden_layers) for n in _LAYER_WEIGHTS}
+        names |= {self._name_of(prm) for _, prm, key in self._head_rows() if key is not None}
         return names - {self._name_of(p_) for p_ in as_fp32}
 
     def fp32_spans(self):
@@ -1379,11 +1420,9 @@ class PretrainEngine(object):
 
     def shard_plan(self, world, rank, bucket_elems=None):
         """The static ownership plan of this engine's slab for `world` ranks (any engine can compute any rank's)."""
-        from .distributed import ShardPlan
-
         f = self.flat
         be = self.bucket_elems if bucket_elems is None else int(bucket_elems)
-        return ShardPlan(f.total, f.n_decay, self.shard_atoms(), self.fp32_spans(), world, rank, be)
+        return distributed.ShardPlan(f.total, f.n_decay, self.shard_atoms(), self.fp32_spans(), world, rank, be)
 
     def _shard_setup(self):
         f = self.flat
@@ -1402,18 +1441,21 @@ class PretrainEngine(object):
                 f.p, grads, self.m_sh, self.v_sh, f.mirror, [(s_, e_, dec, mo) for s_, e_, dec, _, mo in launch.own])
         return tab
 
-    def _shard_reduce(self, launch, handles):
-        """Cast (bf16 communication copy) and reduce-scatter of one launch's ranges; returns the buffer AdamW reads."""
-        from .distributed import reduce_scatter_buckets
-
+    def _comm_copy(self, ranges):
+        """What the communicator reduces for these ranges of the gradient slab -> (buffer, elements per bucket): the fp32 slab
+        itself, or the bf16 communication copy with the ranges cast into it (same bytes per bucket)."""
         if self.g16 is None:
-            reduce_scatter_buckets(self.flat.g, launch, self.plan, self.bucket_elems, self.pg, handles)
-            return self.flat.g
-        for s_, e_ in launch.ranges:
+            return self.flat.g, self.bucket_elems
+        for s_, e_ in ranges:
             if e_ > s_:
                 ops.cast_to_bf16(self.flat.g[s_:e_], self.g16[s_:e_])
-        reduce_scatter_buckets(self.g16, launch, self.plan, 2 * self.bucket_elems, self.pg, handles)
-        return self.g16
+        return self.g16, 2 * self.bucket_elems
+
+    def _shard_reduce(self, launch, handles):
+        """Communication copy and reduce-scatter of one launch's ranges; returns the buffer AdamW reads."""
+        buf, per_bucket = self._comm_copy(launch.ranges)
+        distributed.reduce_scatter_buckets(buf, launch, self.plan, per_bucket, self.pg, handles)
+        return buf
 
     def _shard_update(self, consts, launch, grad_scale, grads):
         """AdamW on this rank's segments of one launch: one kernel launch."""
@@ -1423,11 +1465,9 @@ class PretrainEngine(object):
     def _shard_gather(self, launch, handles):
         """All-gather of one launch's updated pieces: the mirror where a bucket holds bf16-class elements, the fp32
         parameters where it holds fp32-class ones."""
-        from .distributed import all_gather_buckets
-
         f = self.flat
-        all_gather_buckets(f.mirror, [b for b in launch.buckets if b[2]], self.plan, self.pg, handles)
-        all_gather_buckets(f.p, [b for b in launch.buckets if b[3]], self.plan, self.pg, handles)
+        distributed.all_gather_buckets(f.mirror, [b for b in launch.buckets if b[2]], self.plan, self.pg, handles)
+        distributed.all_gather_buckets(f.p, [b for b in launch.buckets if b[3]], self.plan, self.pg, handles)
 
     def _shard_settle(self):
         """The segments this rank does not own, once all gathers have arrived: p = float(mirror) where the weights
@@ -1459,8 +1499,6 @@ class PretrainEngine(object):
         self._adam_end()
 
     def _shard_train_step(self, batch, scale, layers_per_chunk, _force_comm):
-        from .distributed import complement_ranges
-
         ws = self.world
         handles, launched = [], []   # launched: (plan launch, gradient buffer, first handle, one past the last handle)
 
@@ -1477,7 +1515,7 @@ class PretrainEngine(object):
         launch = reduce_ranges if _force_comm is None else local_ranges
         comm = dict(layers_per_chunk=layers_per_chunk, launch=launch, done=[])
         out = self.forward_backward(batch, grad_scale=scale, comm=comm)
-        launch(complement_ranges(self.flat.total, comm["done"]))   # embeddings, region projection
+        launch(distributed.complement_ranges(self.flat.total, comm["done"]))   # embeddings, region projection
         # per arrived range, in launch order: this rank's update, then the all-gather of that range goes out and travels
         # while the next range is updated
         consts = self._adam_begin()
@@ -1500,23 +1538,19 @@ class PretrainEngine(object):
         before fp32-route inference on these weights.  Nothing to do where the optimizer is not sharded."""
         if not self.shard:
             return
-        from .distributed import all_gather_buckets
-
         self._require_ownership()
-        all_gather_buckets(self.flat.p, self.plan.everything().buckets, self.plan, self.pg)
+        distributed.all_gather_buckets(self.flat.p, self.plan.everything().buckets, self.plan, self.pg)
         invalidate_packed_weights()
 
     def _shard_full_moments(self):
         """(m, v) as full slabs on every rank: a collective gather of the shard-local storage (temporaries)."""
-        from .distributed import all_gather_buckets
-
         every = self.plan.everything()
         out = []
         for sh in (self.m_sh, self.v_sh):
             full = torch.zeros(self.flat.total, dtype=torch.float32, device=sh.device)
             for s_, e_, _, _, mo in every.own:
                 full[s_:e_].copy_(sh[mo:mo + e_ - s_])
-            all_gather_buckets(full, every.buckets, self.plan, self.pg)
+            distributed.all_gather_buckets(full, every.buckets, self.plan, self.pg)
             out.append(full)
         return out
 
@@ -1573,13 +1607,7 @@ class PretrainEngine(object):
         if self.shard:
             raise RuntimeError("with the optimizer sharded over the ranks no rank holds the whole reduced gradient slab: call "
                                "optimizer_step(), which reduce-scatters, updates and gathers")
-        from .distributed import all_reduce_flat
-
-        if self.g16 is not None:
-            ops.cast_to_bf16(self.flat.g, self.g16)
-            all_reduce_flat(self.g16, 2 * self.bucket_elems, self.pg)
-        else:
-            all_reduce_flat(self.flat.g, self.bucket_elems, self.pg)
+        distributed.all_reduce_flat(*self._comm_copy([(0, self.flat.total)]), self.pg)
 
     def train_step(self, batch, overlap=True, layers_per_chunk=3, _force_comm=None):
         """zero_grad -> forward -> backward -> gradient all-reduce -> AdamW -> schedule, as pretrain.py:150-193.
@@ -1600,25 +1628,18 @@ class PretrainEngine(object):
             out = self.forward_backward(batch, grad_scale=scale)
             self.all_reduce_grads()
         else:
-            from .distributed import all_reduce_ranges, complement_ranges
-
             handles, launched = [], []   # launched: (ranges, first handle, one past the last handle) per launch call
 
             def reduce_ranges(rng):
                 n0 = len(handles)
-                if self.g16 is None:
-                    all_reduce_ranges(self.flat.g, rng, self.bucket_elems, self.pg, handles)
-                else:
-                    for s_, e_ in rng:   # bf16 communication copy of the range, then its all-reduce (same bytes per bucket)
-                        if e_ > s_:
-                            ops.cast_to_bf16(self.flat.g[s_:e_], self.g16[s_:e_])
-                    all_reduce_ranges(self.g16, rng, 2 * self.bucket_elems, self.pg, handles)
+                buf, per_bucket = self._comm_copy(rng)
+                distributed.all_reduce_ranges(buf, rng, per_bucket, self.pg, handles)
                 launched.append((list(rng), n0, len(handles)))
 
             launch = _force_comm or reduce_ranges
             comm = dict(layers_per_chunk=layers_per_chunk, launch=launch, done=[])
             out = self.forward_backward(batch, grad_scale=scale, comm=comm)
-            launch(complement_ranges(self.flat.total, comm["done"]))  # embeddings, region projection, heads
+            launch(distributed.complement_ranges(self.flat.total, comm["done"]))  # embeddings, region projection, heads
             if _force_comm is None:
                 # AdamW per arrived range, in launch order (last layers first, the embeddings / heads tail last): the update
                 # of the encoder's 85 M parameters runs while the tail's all-reduce is still in flight.  (wait() makes this
@@ -1658,11 +1679,7 @@ class _LossWithGrads(torch.autograd.Function):
                                "step computes the gradients with the forward and keeps ONE set per module -- call "
                                "loss.backward() before the next forward (the reference's loop does: pretrain.py:169-191)")
         f = ctx.engine.flat
-        grads = []
-        for n in ctx.names:
-            g = f.view(f.g, n)
-            grads.append(g * grad_out)
-        return (None, None) + tuple(grads)
+        return (None, None) + tuple(f.view(f.g, n) * grad_out for n in ctx.names)
 
 
 class _LossLazyGrads(torch.autograd.Function):
@@ -1692,6 +1709,19 @@ class _LossLazyGrads(torch.autograd.Function):
         return (None, None, None) + tuple(f.view(f.g, eng._name_of(p)) * grad_out for p in ctx.params)
 
 
+def _trunk_param_grads(eng, st, names, d_pooled):
+    """What a trunk autograd node hands back for its parameters after eng.trunk_backward: copies of the slab's gradients, None
+    for the groups that backward had nothing to feed (the region projection of a text-only forward, the pooler when nothing
+    read pooled_output)."""
+    unused = ()
+    if st.img is None:
+        unused += ("bert.img_embedding.", "bert.location_embeds.", "bert.LayerNorm.")
+    if d_pooled is None:
+        unused += ("bert.pooler.",)
+    f = eng.flat
+    return tuple(None if n.startswith(unused) else f.view(f.g, n).clone() for n in names)
+
+
 class _TrunkWithGrads(torch.autograd.Function):
     """The trunk as ONE autograd node for callers that train through it (OscarEncoder in the rollout, agent.py:493-518):
     forward = the engine's trunk forward (activations kept in its buffers), backward = its trunk backward, handing the
@@ -1701,11 +1731,8 @@ class _TrunkWithGrads(torch.autograd.Function):
     def forward(ctx, engine, batch, head_mask, unmasked_only, want_hidden, want_attn, n_history, *tensors):
         # tensors: the n_history encoder_history_states (inputs with gradients of their own), then the parameters
         history, params = tensors[:n_history], tensors[n_history:]
-        if n_history:
-            out = engine.trunk_forward(batch, head_mask, unmasked_only=unmasked_only, want_hidden=want_hidden,
-                                       want_attn=want_attn, history=history)
-        else:
-            out = engine.trunk_forward(batch, head_mask, unmasked_only=unmasked_only, want_hidden=want_hidden, want_attn=want_attn)
+        out = engine.trunk_forward(batch, head_mask, unmasked_only=unmasked_only, want_hidden=want_hidden, want_attn=want_attn,
+                                   history=history)
         seq, pooled, st = out[:3]
         ctx.engine, ctx.st = engine, st
         ctx.history_like = [(h.dtype, h.device) for h in history]
@@ -1721,16 +1748,9 @@ class _TrunkWithGrads(torch.autograd.Function):
         eng, st = ctx.engine, ctx.st
         d_hidden = d_rest[:ctx.n_hidden]
         eng.trunk_backward(st, d_seq, d_pooled, d_hidden=list(d_hidden) if d_hidden else None)
-        f = eng.flat
-        unused = set()
-        if st.img is None:
-            unused.update(("bert.img_embedding.", "bert.location_embeds.", "bert.LayerNorm."))
-        if d_pooled is None:
-            unused.add("bert.pooler.")
-        grads = [None if n.startswith(tuple(unused)) else f.view(f.g, n).clone() for n in ctx.names]
         d_history = tuple(None if d is None else d.to(device=dev, dtype=dt)
                           for d, (dt, dev) in zip(st.d_history or (), ctx.history_like))
-        return (None, None, None, None, None, None, None) + d_history + tuple(grads)
+        return (None, None, None, None, None, None, None) + d_history + _trunk_param_grads(eng, st, ctx.names, d_pooled)
 
 
 class _TrunkLazyGrads(torch.autograd.Function):
@@ -1749,15 +1769,7 @@ class _TrunkLazyGrads(torch.autograd.Function):
         eng = _bridge_engine(ctx.trunk)
         _, _, st = eng.trunk_forward(ctx.batch, ctx.head_mask, training=False)
         eng.trunk_backward(st, d_seq, d_pooled)
-        f = eng.flat
-        unused = []
-        if st.img is None:
-            unused += ["bert.img_embedding.", "bert.location_embeds.", "bert.LayerNorm."]
-        if d_pooled is None:
-            unused.append("bert.pooler.")
-        names = [eng._name_of(p) for p in ctx.params]
-        grads = [None if n.startswith(tuple(unused)) else f.view(f.g, n).clone() for n in names]
-        return (None, None, None, None, None) + tuple(grads)
+        return (None, None, None, None, None) + _trunk_param_grads(eng, st, [eng._name_of(p) for p in ctx.params], d_pooled)
 
 
 def lazy_autograd_trunk(trunk, batch, head_mask, seq, pooled):
@@ -1777,21 +1789,14 @@ def autograd_trunk_forward(trunk, batch, head_mask=None, unmasked_only=False, wa
     eng = _bridge_engine(trunk)
     history = list(history) if history else []
     if not torch.is_grad_enabled():
-        kw = dict(history=history) if history else {}
-        out = eng.trunk_forward(batch, head_mask, unmasked_only=unmasked_only, want_hidden=want_hidden, want_attn=want_attn, **kw)
+        out = eng.trunk_forward(batch, head_mask, unmasked_only=unmasked_only, want_hidden=want_hidden, want_attn=want_attn,
+                                history=history)
         return (out[0], out[1]) + ((tuple(out[3]),) if want_hidden else ()) + ((tuple(out[4]),) if want_attn else ())
     params = [p for p in trunk.parameters() if p.requires_grad]
     out = _TrunkWithGrads.apply(eng, batch, head_mask, bool(unmasked_only), bool(want_hidden), bool(want_attn), len(history),
                                 *history, *params)
-    L1 = trunk.config.num_hidden_layers + 1
-    res = (out[0], out[1])
-    k = 2
-    if want_hidden:
-        res = res + (tuple(out[k:k + L1]),)
-        k += L1
-    if want_attn:
-        res = res + (tuple(out[k:]),)
-    return res
+    k = 2 + (trunk.config.num_hidden_layers + 1 if want_hidden else 0)
+    return (out[0], out[1]) + ((tuple(out[2:k]),) if want_hidden else ()) + ((tuple(out[k:]),) if want_attn else ())
 
 
 def _bridge_engine(model):

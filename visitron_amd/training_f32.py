@@ -20,15 +20,11 @@ their plain form.  Not served: several ranks, row compaction, intermediate hidde
 """
 import torch
 
-from . import ops
+from . import ops, training
 from .modeling import _head_scale, _i64
 from .ops import ACT_GELU, ACT_TANH, round_up
 
 F32 = torch.float32
-
-
-class _St(object):
-    pass
 
 
 def setup(eng):
@@ -61,26 +57,16 @@ def _dgrad(dy, w, K=None, lda=None, residual=None):
 
 
 def _layer_params(eng, l):
-    f, H = eng.flat, eng.cfg.hidden_size
-    pre = "bert.encoder.layer.%d." % l
-    qw, qb = pre + "attention.self.query.weight", pre + "attention.self.query.bias"
-    names = dict(w_ao="attention.output.dense.weight", b_ao="attention.output.dense.bias",
-                 ln1_g="attention.output.LayerNorm.weight", ln1_b="attention.output.LayerNorm.bias",
-                 w_in="intermediate.dense.weight", b_in="intermediate.dense.bias", w_out="output.dense.weight",
-                 b_out="output.dense.bias", ln2_g="output.LayerNorm.weight", ln2_b="output.LayerNorm.bias")
-    w = dict(w_qkv=f.view(f.p, qw, 3 * H * H, (3 * H, H)), b_qkv=f.view(f.p, qb, 3 * H, (3 * H,)))
-    g = dict(w_qkv=f.view(f.g, qw, 3 * H * H, (3 * H, H)), b_qkv=f.view(f.g, qb, 3 * H, (3 * H,)))
-    for k, n in names.items():
-        w[k], g[k] = f.view(f.p, pre + n), f.view(f.g, pre + n)
-    return w, g
+    """(parameters, gradients) of encoder layer l as {field: fp32 view} (training._LAYER_FIELDS, the packed projection)."""
+    f = eng.flat
+    return training._layer_views(f, l, f.p, f.p), training._layer_views(f, l, f.g, f.g)
 
 
-def trunk_forward(eng, batch, head_mask, training):
+def trunk_forward(eng, batch, head_mask, is_training):
     """Embeddings, region projection, encoder layers and pooler in fp32, every activation the backward reads kept."""
     m, cfg = eng.model, eng.cfg
     eng._require_ownership()
     eng.flat.reattach_grads()
-    st = _St()
     ids = _i64(batch["input_ids"])
     dev = ids.device
     B, T = ids.shape
@@ -102,8 +88,8 @@ def trunk_forward(eng, batch, head_mask, training):
             mode = 0          # (1 - m) * -10000 inside the softmax kernel (encoder.py:238-241)
     hs = _head_scale(head_mask, L, nh, dev)
     tt, pos_ids = _i64(batch.get("token_type_ids")), _i64(batch.get("position_ids"))
-    p_h = float(cfg.hidden_dropout_prob) if training else 0.0
-    p_a = float(cfg.attention_probs_dropout_prob) if training else 0.0
+    p_h = float(cfg.hidden_dropout_prob) if is_training else 0.0
+    p_a = float(cfg.attention_probs_dropout_prob) if is_training else 0.0
     seed = (eng.drop_seed_base + eng.fb_count) & 0xFFFFFFFFFFFFFFFF
     eng.fb_count += 1
     eng.last_drop_seed = seed
@@ -162,15 +148,9 @@ def trunk_forward(eng, batch, head_mask, training):
     pool = m.bert.pooler.dense
     pooled = _linear(cur, _d(pool.weight), _d(pool.bias), M=B, lda=S * H, act=ACT_TANH)
     eng._fwd_serial += 1
-    st.__dict__.update(B=B, T=T, R=R, S=S, H=H, nh=nh, L=L, M=M, dev=dev, mask=mask, mode=mode, hs=hs, p_h=p_h, p_a=p_a,
-                       seed=seed, ids=ids, tt=tt, pos_ids=pos_ids, e=e, x0=x0, img=img, a_img=a_img, img_pre=img_pre,
-                       layers=layers, seq=cur, pooled=pooled, serial=eng._fwd_serial)
-    return st
-
-
-def _zero(eng, params):
-    for p in params:
-        eng._grad(p).zero_()
+    return training.TrunkState(B=B, T=T, R=R, S=S, H=H, nh=nh, L=L, M=M, dev=dev, serial=eng._fwd_serial, mask=mask, mode=mode,
+                               hs=hs, p_h=p_h, p_a=p_a, seed=seed, ids=ids, tt=tt, pos_ids=pos_ids, img=img, a_img=a_img,
+                               img_pre=img_pre, e=e, x0=x0, layers=layers, seq=cur, pooled=pooled)
 
 
 def pooler_backward(eng, st, g, d_pooled, acc):
@@ -246,14 +226,12 @@ def trunk_backward(eng, st, g, acc, word_grad_ready=False):
     ops.embed_table_grad(typ.reshape(-1), de, type_grad)
 
     bt = m.bert
-    has_ln = bool(getattr(bt, "use_img_layernorm", None))
     if st.img is None:
         if not acc:
-            _zero(eng, (bt.img_embedding.weight, bt.img_embedding.bias, bt.location_embeds.weight, bt.location_embeds.bias)
-                  + ((bt.LayerNorm.weight, bt.LayerNorm.bias) if has_ln else ()))
+            eng._zero_head_grads("region")
         return
     d_img = torch.empty((B * R, H), dtype=F32, device=dev)
-    if has_ln:
+    if st.img_pre is not None:
         ops.layernorm_bwd_f32(st.img_pre, g[T:], _d(bt.LayerNorm.weight), bt.LayerNorm.variance_epsilon,
                               eng._grad(bt.LayerNorm.weight), eng._grad(bt.LayerNorm.bias), dx=d_img, accumulate=acc, M=B * R,
                               grp_rows=R, grp_stride=S, drop_in=(p_h, seed, ops.SITE_IMG))
@@ -325,11 +303,12 @@ def forward_backward(eng, batch, grad_scale, accumulate, head_mask, backward):
     acc = bool(accumulate)
     emb = m.bert.embeddings
     g = torch.zeros((M, H), dtype=F32, device=dev)
-    dec_tied = pr.decoder.weight is emb.word_embeddings.weight
+    dec_tied = eng._decoder_tied()
     if not acc:
         eng._grad(emb.word_embeddings.weight).zero_()   # the tied decoder accumulates into it; the tables add to it later
-        eng._grad(pr.bias).zero_()
     if Ml > 0:
+        if not acc:
+            eng._grad(pr.bias).zero_()                  # shares the accumulate flag of the decoder weight below
         ops.wgrad_f32(dl[:, :V], t2, eng._grad(pr.decoder.weight), eng._grad(pr.bias), accumulate=acc or dec_tied)
         g_t2 = _dgrad(dl, _d(pr.decoder.weight), K=V)
         g_t1 = torch.empty((Ml, H), dtype=F32, device=dev)
@@ -340,20 +319,17 @@ def forward_backward(eng, batch, grad_scale, accumulate, head_mask, backward):
         ops.wgrad_f32(g_h, seq_w, eng._grad(pr.transform.dense.weight), eng._grad(pr.transform.dense.bias), accumulate=acc)
         g.index_add_(0, idx_w, _dgrad(g_h, _d(pr.transform.dense.weight)))
     elif not acc:
-        # no supervised MLM row (the loss is NaN, as the reference's): the head's gradients are zero
-        _zero(eng, (pr.transform.dense.weight, pr.transform.dense.bias, pr.transform.LayerNorm.weight,
-                    pr.transform.LayerNorm.bias) + (() if dec_tied else (pr.decoder.weight,)))
+        eng._zero_head_grads("mlm")   # no supervised MLM row (the loss is NaN, as the reference's): zero gradients
     if Mt > 0:
         ops.wgrad_f32(dlt[:, :C], seq_t, eng._grad(lin_tok.weight), eng._grad(lin_tok.bias), accumulate=acc)
         g.index_add_(0, idx_t, _dgrad(dlt, _d(lin_tok.weight), K=C))
     elif not acc:
-        _zero(eng, (lin_tok.weight, lin_tok.bias))
+        eng._zero_head_grads("token")
     if dla is not None:
         ops.wgrad_f32(dla[:, :A], st.pooled, eng._grad(m.next_action.linear.weight), eng._grad(m.next_action.linear.bias),
                       accumulate=acc)
         pooler_backward(eng, st, g, _dgrad(dla, _d(m.next_action.linear.weight), K=A), acc)
     elif not acc:
-        _zero(eng, (m.next_action.linear.weight, m.next_action.linear.bias, m.bert.pooler.dense.weight,
-                    m.bert.pooler.dense.bias))
+        eng._zero_head_grads("action", "pooler")
     trunk_backward(eng, st, g, acc, word_grad_ready=True)
     return out
