@@ -472,8 +472,9 @@ int vt_lstm_sequence_rows_f32(const float* xproj, int64_t ldx_row, const int32_t
 
 /* out[M,N] (fp32) = act([x0 | x1] . W^T + bias) for a handful of rows: the dense layers of the decoder step
  * (AttnDecoderLSTM.forward, agent_models.py:406-425; SoftDotAttention.linear_in / linear_out :336, :354-355 with its
- * torch.cat folded in).  x0 [M,K0], x1 [M,K1] (optional) fp32 with K0, K1 multiples of 4; W bf16 [N, Kpad] zero-padded
- * past K0 + K1, Kpad a multiple of 32; act 0 = none, 2 = tanh. */
+ * torch.cat folded in).  x0 [M,K0], x1 [M,K1] (optional) fp32 of any widths K0 >= 1, K1 >= 0 and any row strides (read by
+ * address: 16-, 8- or 4-byte loads, nothing outside a row's own columns); any N; W bf16 [N, Kpad] zero-padded past K0 + K1,
+ * Kpad a multiple of 32, ldw a multiple of 8, 16-byte aligned; act 0 = none, 2 = tanh. */
 int vt_skinny_linear_f32(const float* x0, int64_t ld0, int K0, const float* x1, int64_t ld1, int K1, const void* w,
                          int64_t ldw, const float* bias, float* out, int64_t ldo, int M, int N, int Kpad, int act,
                          vt_stream_t stream);
@@ -482,7 +483,8 @@ int vt_skinny_linear_f32(const float* x0, int64_t ld0, int K0, const float* x1, 
  * mask (uint8 [B,L], nonzero = masked) -> -inf; softmax over l; weighted[b,:] = sum_l p[l] context[b,l,:].
  * context fp32 with element strides ld_batch / ld_row.  weighted (optional) fp32 [B,D]; attn (optional) fp32 [B,L]
  * receives the probabilities (output_prob != 0) or the masked logits (the reference's `logit` aliases the masked
- * tensor, :339-343). */
+ * tensor, :339-343).  Any 1 <= D <= 4096 and L <= 8192; the load width follows D, the strides and the bases (16 bytes for
+ * multiples of 4, 8 bytes for D % 4 == 2 such as 2058, else 4) and no element outside [0, D) of a row is read. */
 int vt_softdot_attention_f32(const float* target, const float* context, int64_t ld_batch, int64_t ld_row,
                              const uint8_t* mask, float* weighted, float* attn, int B, int L, int D, int output_prob,
                              vt_stream_t stream);

@@ -7,9 +7,11 @@
 // first is stored (8 rounds x 64 lanes x 16 bytes = the shipped 2048-float row in one go, without a predicate or a branch
 // between the 8 loads and the 8 stores; a width that leaves fewer than 8 rounds over takes them in a second, predicated
 // group, whose stores the compiler separates by full waits), and the angle tail is one more 16-byte store by the lane whose
-// turn it is.  Any other D (the reference's default 2054: rows start 8-byte aligned on every
-// other row only) goes element by element.  A zero row (END, padding, bad index) is stores only.  Every access is predicated
-// on the row's own bounds: no piece index reaches D / 4 on the source side or D / 4 + 1 on the destination side.
+// turn it is.  An even D that is no multiple of 4 (the reference's default 2054) with 8-byte aligned bases leaves every row
+// 8-byte aligned: the same shape with 8-byte pieces (W = 2: 8 rounds x 64 lanes x 8 bytes, two such groups and a rest for
+// 2054 floats) and the tail as two 8-byte stores.  An odd D, or outputs aligned to less, goes element by element.  A zero
+// row (END, padding, bad index) is stores only.  Every access is predicated on the row's own bounds: no piece index reaches
+// D / W on the source side, and the tail ends at D + 4 on the destination side.
 #include "dispatch.hpp"
 
 #define OBS_ROUNDS 8
@@ -26,22 +28,28 @@ __device__ __forceinline__ f32x4 obs_angle(double h, double e, int lane, int own
 // One output row: the image part (src is null for a zero row) and, where h and e point at a candidate's heading and
 // elevation, the row's angle tail, evaluated after the first loads have been issued and before they are stored, so the
 // float64 arithmetic runs under the loads' latency.  -> the tail on lane `owner`.
-template <bool VEC>
+template <int W> struct ObsPiece { typedef float type; };
+template <> struct ObsPiece<4> { typedef f32x4 type; };
+template <> struct ObsPiece<2> { typedef f32x2 type; };
+
+// W = floats per piece: 4, 2 or 1 (element by element)
+template <int W>
 __device__ __forceinline__ f32x4 obs_copy_row(const float* __restrict__ src, float* __restrict__ dst, int D, int lane,
                                               f32x4 tail, const double* h, const double* e, int owner) {
+  typedef typename ObsPiece<W>::type piece;
   bool pending = h != nullptr;
-  if (VEC) {
-    const int np = D >> 2;
-    const f32x4* s4 = (const f32x4*)src;
-    f32x4* d4 = (f32x4*)dst;
+  if (W > 1) {
+    const int np = D / W;
+    const piece* s4 = (const piece*)src;
+    piece* d4 = (piece*)dst;
     if (!src) {
-      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+      const piece z = {};
       for (int p = lane; p < np; p += 64) d4[p] = z;
       return tail;
     }
     int p0 = 0;
     for (; p0 + 64 * OBS_ROUNDS <= np; p0 += 64 * OBS_ROUNDS) {   // whole groups of rounds: no predicate inside
-      f32x4 r[OBS_ROUNDS];
+      piece r[OBS_ROUNDS];
 #pragma unroll
       for (int k = 0; k < OBS_ROUNDS; ++k) r[k] = s4[p0 + k * 64 + lane];
       if (pending) { tail = obs_angle(*h, *e, lane, owner); pending = false; }
@@ -51,14 +59,14 @@ __device__ __forceinline__ f32x4 obs_copy_row(const float* __restrict__ src, flo
     // the rest, fewer than 8 rounds: the round count is the wave's, the last round's idle lanes are switched off
     const int nr = (np - p0 + 63) >> 6;
     if (nr > 0) {
-      f32x4 r[OBS_ROUNDS - 1];
+      piece r[OBS_ROUNDS - 1];
 #pragma unroll
       for (int k = 0; k < OBS_ROUNDS - 1; ++k) {
         const int p = p0 + k * 64 + lane;
         if (k < nr - 1) r[k] = s4[p];
       }
       const int pl = p0 + (nr - 1) * 64 + lane;
-      f32x4 last = {0.f, 0.f, 0.f, 0.f};
+      piece last = {};
       if (pl < np) last = s4[pl];
       if (pending) { tail = obs_angle(*h, *e, lane, owner); pending = false; }
 #pragma unroll
@@ -75,18 +83,21 @@ __device__ __forceinline__ f32x4 obs_copy_row(const float* __restrict__ src, flo
   return tail;
 }
 
-// the 4 floats behind the image part, held by lane `owner`: one 16-byte store, or four 4-byte stores
-template <bool VEC>
+// the 4 floats behind the image part, held by lane `owner`: one 16-byte store, two 8-byte stores or four 4-byte stores
+template <int W>
 __device__ __forceinline__ void obs_store_tail(float* dst, int D, f32x4 v, int lane, int owner) {
   if (lane != owner) return;
-  if (VEC) {
+  if (W == 4) {
     *(f32x4*)(dst + D) = v;
+  } else if (W == 2) {
+    *(f32x2*)(dst + D) = (f32x2){v[0], v[1]};
+    *(f32x2*)(dst + D + 2) = (f32x2){v[2], v[3]};
   } else {
     dst[D] = v[0]; dst[D + 1] = v[1]; dst[D + 2] = v[2]; dst[D + 3] = v[3];
   }
 }
 
-template <bool VEC>
+template <int W>
 __global__ __launch_bounds__(256) void obs_gather_kernel(ObsGatherArgs a) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -105,7 +116,7 @@ __global__ __launch_bounds__(256) void obs_gather_kernel(ObsGatherArgs a) {
     }
     bad = __ballot(out) != 0;
   }
-  const int owner = VEC ? ((D >> 2) & 63) : 0;   // the lane that holds and stores the row's tail
+  const int owner = W > 1 ? ((D / W) & 63) : 0;   // the lane that holds and stores the row's tail
   if (r < R) {
     const long ldo = (long)D + 4;
     float* dst;
@@ -118,7 +129,7 @@ __global__ __launch_bounds__(256) void obs_gather_kernel(ObsGatherArgs a) {
       if (!bad) {
         src = a.store + ((long)slot * V + r) * D;
         const float* t = a.table + ((long)view * V + r) * 4;
-        if (lane == owner) tail = VEC ? *(const f32x4*)t : (f32x4){t[0], t[1], t[2], t[3]};
+        if (lane == owner) tail = W > 1 ? *(const f32x4*)t : (f32x4){t[0], t[1], t[2], t[3]};   // (the table is 16-byte aligned)
       }
     } else {
       const int j = r - V;
@@ -129,8 +140,8 @@ __global__ __launch_bounds__(256) void obs_gather_kernel(ObsGatherArgs a) {
         e = a.cand_e + (long)b * Cmax + j;
       }
     }
-    tail = obs_copy_row<VEC>(src, dst, D, lane, tail, h, e, owner);
-    obs_store_tail<VEC>(dst, D, tail, lane, owner);
+    tail = obs_copy_row<W>(src, dst, D, lane, tail, h, e, owner);
+    obs_store_tail<W>(dst, D, tail, lane, owner);
   }
   if (g == 0 && wave == 0) {   // the per-agent outputs, behind this wave's row
     const int leng = (count < 0 ? 0 : (count >= Cmax ? Cmax - 1 : count)) + 1;
@@ -154,14 +165,16 @@ int vt_obs_gather_dispatch(const ObsGatherArgs& a, hipStream_t stream) {
   const long groups = (long)a.B * (((long)a.V + a.Cmax + 3) / 4);
   if (groups > 0x7fffffffL) return VT_ERR_BAD_SHAPE;
   const bool vec = (a.D & 3) == 0 && ((((uintptr_t)a.f_t) | ((uintptr_t)a.cand)) & 15) == 0;
-  if (vec) hipLaunchKernelGGL(obs_gather_kernel<true>, dim3((unsigned)groups), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL(obs_gather_kernel<false>, dim3((unsigned)groups), dim3(256), 0, stream, a);
+  const bool vec2 = !vec && (a.D & 1) == 0 && ((((uintptr_t)a.f_t) | ((uintptr_t)a.cand)) & 7) == 0;
+  if (vec) hipLaunchKernelGGL(obs_gather_kernel<4>, dim3((unsigned)groups), dim3(256), 0, stream, a);
+  else if (vec2) hipLaunchKernelGGL(obs_gather_kernel<2>, dim3((unsigned)groups), dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL(obs_gather_kernel<1>, dim3((unsigned)groups), dim3(256), 0, stream, a);
   return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
 }
 
 // ---------------------------------------------------------------------------------------------
 // out[b, :] = store[slot_b, view_b, :]: one wave per row, four rows per workgroup
-template <bool VEC>
+template <int W>
 __global__ __launch_bounds__(256) void obs_view_kernel(ObsViewArgs a) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -171,7 +184,7 @@ __global__ __launch_bounds__(256) void obs_view_kernel(ObsViewArgs a) {
   const bool bad = slot < 0 || slot >= a.N || view < 0 || view >= a.V;
   if (bad && a.err && lane == 0) *a.err = 1;
   const float* src = bad ? nullptr : a.store + ((long)slot * a.V + view) * a.D;
-  obs_copy_row<VEC>(src, a.out + (long)row * a.ld_out, a.D, lane, (f32x4){0.f, 0.f, 0.f, 0.f}, nullptr, nullptr, 0);
+  obs_copy_row<W>(src, a.out + (long)row * a.ld_out, a.D, lane, (f32x4){0.f, 0.f, 0.f, 0.f}, nullptr, nullptr, 0);
 }
 
 int vt_obs_gather_view_dispatch(const ObsViewArgs& a, hipStream_t stream) {
@@ -180,8 +193,10 @@ int vt_obs_gather_view_dispatch(const ObsViewArgs& a, hipStream_t stream) {
   if (((uintptr_t)a.store) & 15) return VT_ERR_BAD_ALIGN;
   if ((((uintptr_t)a.rows) | ((uintptr_t)a.out)) & 3) return VT_ERR_BAD_ALIGN;
   const bool vec = (a.D & 3) == 0 && (a.ld_out & 3) == 0 && (((uintptr_t)a.out) & 15) == 0;
+  const bool vec2 = !vec && (a.D & 1) == 0 && (a.ld_out & 1) == 0 && (((uintptr_t)a.out) & 7) == 0;
   const unsigned groups = (unsigned)((a.B + 3) / 4);
-  if (vec) hipLaunchKernelGGL(obs_view_kernel<true>, dim3(groups), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL(obs_view_kernel<false>, dim3(groups), dim3(256), 0, stream, a);
+  if (vec) hipLaunchKernelGGL(obs_view_kernel<4>, dim3(groups), dim3(256), 0, stream, a);
+  else if (vec2) hipLaunchKernelGGL(obs_view_kernel<2>, dim3(groups), dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL(obs_view_kernel<1>, dim3(groups), dim3(256), 0, stream, a);
   return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
 }

@@ -4,8 +4,11 @@
 //   * AttnDecoderLSTM.forward :384-428  -- nn.LSTMCell = one lstm_step, three softdot_attention
 // The dense projections of these modules go through the NT GEMM (gemm_bf16.hip); what is here is the part with no
 // GEMM shape: the recurrent product h . W_hh^T fused with the gate arithmetic, and the batched dot / softmax / weighted
-// sum over a short context.
+// sum over a short context.  The feature width D of the attentions and the input widths of skinny_linear are free (the
+// reference's default is 2058 = 2 mod 4): each kernel picks its load width from the rows' alignment and keeps, for aligned
+// multiples of 4, the code those shapes always ran.
 #include "dispatch.hpp"
+#include "row_loads.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // One LSTM time step (torch.nn.LSTM / LSTMCell semantics, gate order i, f, g, o):
@@ -240,17 +243,45 @@ int vt_lstm_sequence_bwd_dispatch(const float* d_seq_out, long ldd_b, long ldd_t
 //   p = softmax(attn) over l (:344)                                   weighted[b, :] = sum_l p[l] context[b, l, :] (:349)
 // One workgroup per batch row; logits / probabilities live in LDS.  fp32 throughout (the context is the caller's
 // fp32 feature tensor: the kernel is a pure read of it, twice, the second time from L2).
+//
+// Any 1 <= D <= 4096 and any strides >= D.  The load width follows the rows' alignment, one choice per launch:
+//   vec   D % 4 == 0, strides % 4 == 0, bases 16-byte aligned: 16-byte pieces (every shipped width: 2052, 512, 132)
+//   vec2  D % 4 == 2, strides even, bases 8-byte aligned (the reference's default 2058: a row is 8-byte aligned whenever
+//         its base is): the same groups of 4 columns as vec, each read as two 8-byte pieces; the last group of a row has 2
+//   else  element by element (odd D, odd strides, or a misaligned base; a misaligned row of a width that is a multiple
+//         of 4 stays here, as it always was)
+// so no load touches an element outside [0, D) of a row.  In the weighted-sum phase a thread walks the column groups of
+// its key part in steps of the threads a part has, which serves every D in the element form too.
 
 #define SD_WAVES 16
+#define SD_THREADS (64 * SD_WAVES)
+// column groups of a row, threads per key part and key parts for the weighted-sum / d_target phases (host and device)
+__host__ __device__ __forceinline__ int sd_groups(int D, int gw) { return (D + gw - 1) / gw; }
+__host__ __device__ __forceinline__ int sd_part_threads(int G) { return G < SD_THREADS ? G : SD_THREADS; }
+__host__ __forceinline__ int sd_parts(int G, int L) {
+  int parts = SD_THREADS / sd_part_threads(G);
+  if (parts > 8) parts = 8;                          // 8 x D floats of LDS
+  if (parts > L) parts = L;
+  return parts;
+}
+// the partial-sum area behind `floats` floats of LDS: at the next 16-byte boundary (it is accessed in 8- and 16-byte pieces)
+__host__ __device__ __forceinline__ int sd_carve(int floats) { return (floats + 3) & ~3; }
+
+__host__ __device__ __forceinline__ bool sd_aligned(const SoftDotArgs& a, int w) {   // w = 4 or 2 floats per piece
+  return ((a.ld_row & (w - 1)) == 0) && ((a.ld_batch & (w - 1)) == 0) &&
+         ((((uintptr_t)a.context) | ((uintptr_t)a.target)) & (4 * w - 1)) == 0;
+}
+
 __global__ __launch_bounds__(64 * SD_WAVES) void softdot_kernel(SoftDotArgs a, int parts) {
-  extern __shared__ float sl[];          // [L] logits -> probabilities | [2 * SD_WAVES] reduction scratch | [parts][D] partial sums
+  // [L] logits -> probabilities | [2 * SD_WAVES] reduction scratch | (to 16 bytes) [parts][D] partial sums
+  extern __shared__ __attribute__((aligned(16))) float sl[];
   float* red = sl + a.L;
-  float* psum = red + 2 * SD_WAVES;
+  float* psum = sl + sd_carve(a.L + 2 * SD_WAVES);
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* ctx = a.context + (long)b * a.ld_batch;
   const float* tg = a.target + (long)b * a.D;
-  const bool vec = ((a.D & 3) == 0) && ((a.ld_row & 3) == 0) && ((a.ld_batch & 3) == 0) &&
-                   ((((uintptr_t)a.context) | ((uintptr_t)a.target)) & 15) == 0;
+  const bool vec = ((a.D & 3) == 0) && sd_aligned(a, 4);
+  const bool vec2 = ((a.D & 3) == 2) && sd_aligned(a, 2);
   for (int l = wave; l < a.L; l += SD_WAVES) {
     const float* row = ctx + (long)l * a.ld_row;
     float s = 0.f;
@@ -258,6 +289,13 @@ __global__ __launch_bounds__(64 * SD_WAVES) void softdot_kernel(SoftDotArgs a, i
       for (int d = lane * 4; d < a.D; d += 256) {
         const f32x4 c = *(const f32x4*)(row + d), t = *(const f32x4*)(tg + d);
         s += c[0] * t[0] + c[1] * t[1] + c[2] * t[2] + c[3] * t[3];
+      }
+    } else if (vec2) {
+      for (int d = lane * 4; d < a.D; d += 256) {
+        const f32x2 c = *(const f32x2*)(row + d), t = *(const f32x2*)(tg + d);
+        f32x2 c1 = {0.f, 0.f}, t1 = {0.f, 0.f};
+        if (d + 2 < a.D) { c1 = *(const f32x2*)(row + d + 2); t1 = *(const f32x2*)(tg + d + 2); }
+        s += c[0] * t[0] + c[1] * t[1] + c1[0] * t1[0] + c1[1] * t1[1];
       }
     } else {
       for (int d = lane; d < a.D; d += 64) s += row[d] * tg[d];
@@ -306,10 +344,10 @@ __global__ __launch_bounds__(64 * SD_WAVES) void softdot_kernel(SoftDotArgs a, i
   if (!a.weighted) return;
   // weighted[d] = sum_l p[l] ctx[l][d]: thread = (column group g, key part): part sums every parts-th key, the parts
   // meet in LDS.  A masked key carries probability exactly 0 and is skipped (0 * inf must not appear).
-  const int gw = vec ? 4 : 1;
-  const int G = (a.D + gw - 1) / gw;
-  const int g = tid % G, part = tid / G;
-  if (tid < G * parts) {
+  const int gw = (vec || vec2) ? 4 : 1;
+  const int G = sd_groups(a.D, gw), gt = sd_part_threads(G);   // vec: G <= 1024 = gt, one group per thread
+  const int g = tid % gt, part = tid / gt;
+  if (tid < gt * parts) {
     if (vec) {
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       for (int l = part; l < a.L; l += parts) {
@@ -320,13 +358,32 @@ __global__ __launch_bounds__(64 * SD_WAVES) void softdot_kernel(SoftDotArgs a, i
         }
       }
       *(f32x4*)(psum + (long)part * a.D + 4 * g) = acc;
-    } else {
-      float acc = 0.f;
+    } else if (vec2) {
+      const bool whole = 4 * g + 2 < a.D;   // (G <= 1024 = gt: one group per thread, as in vec; the row's last group has 2 columns)
+      f32x2 acc = {0.f, 0.f}, acc1 = {0.f, 0.f};
       for (int l = part; l < a.L; l += parts) {
         const float p = sl[l];
-        if (p != 0.f) acc += p * ctx[(long)l * a.ld_row + g];
+        if (p != 0.f) {
+          const float* cp = ctx + (long)l * a.ld_row + 4 * g;
+          const f32x2 c = *(const f32x2*)cp;
+          acc[0] += p * c[0]; acc[1] += p * c[1];
+          if (whole) {
+            const f32x2 c1 = *(const f32x2*)(cp + 2);
+            acc1[0] += p * c1[0]; acc1[1] += p * c1[1];
+          }
+        }
       }
-      psum[(long)part * a.D + g] = acc;
+      *(f32x2*)(psum + (long)part * a.D + 4 * g) = acc;
+      if (whole) *(f32x2*)(psum + (long)part * a.D + 4 * g + 2) = acc1;
+    } else {
+      for (int gg = g; gg < G; gg += gt) {
+        float acc = 0.f;
+        for (int l = part; l < a.L; l += parts) {
+          const float p = sl[l];
+          if (p != 0.f) acc += p * ctx[(long)l * a.ld_row + gg];
+        }
+        psum[(long)part * a.D + gg] = acc;
+      }
     }
   }
   __syncthreads();
@@ -340,16 +397,12 @@ __global__ __launch_bounds__(64 * SD_WAVES) void softdot_kernel(SoftDotArgs a, i
 int vt_softdot_dispatch(const SoftDotArgs& a, hipStream_t stream) {
   if (!a.target || !a.context) return VT_ERR_NULL;
   if (!a.weighted && !a.attn) return VT_ERR_NULL;
-  if (a.B <= 0 || a.L <= 0 || a.D <= 0 || a.L > 8192) return VT_ERR_BAD_SHAPE;
+  if (a.B <= 0 || a.L <= 0 || a.D <= 0 || a.L > 8192 || a.D > 4096) return VT_ERR_BAD_SHAPE;
   if (a.weighted && (((uintptr_t)a.weighted) & 15)) return VT_ERR_BAD_ALIGN;
-  const bool vec = ((a.D & 3) == 0) && ((a.ld_row & 3) == 0) && ((a.ld_batch & 3) == 0) &&
-                   ((((uintptr_t)a.context) | ((uintptr_t)a.target)) & 15) == 0;
-  const int G = vec ? a.D / 4 : a.D;
-  if (G > 64 * SD_WAVES) return VT_ERR_BAD_SHAPE;   // D <= 4096 (1024 unaligned)
-  int parts = (64 * SD_WAVES) / G;
-  if (parts > 8) parts = 8;                          // 8 x D floats of LDS
-  if (parts > a.L) parts = a.L;
-  const size_t lds = ((size_t)a.L + 2 * SD_WAVES + (size_t)parts * a.D) * sizeof(float);
+  const bool vec = ((a.D & 3) == 0) && sd_aligned(a, 4);
+  const bool vec2 = ((a.D & 3) == 2) && sd_aligned(a, 2);
+  const int parts = sd_parts(sd_groups(a.D, (vec || vec2) ? 4 : 1), a.L);
+  const size_t lds = ((size_t)sd_carve(a.L + 2 * SD_WAVES) + (size_t)parts * a.D) * sizeof(float);
   if (lds > 64 * 1024 &&
       hipFuncSetAttribute((const void*)softdot_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return VT_ERR_HIP;
@@ -364,11 +417,21 @@ int vt_softdot_dispatch(const SoftDotArgs& a, hipStream_t stream) {
 //             masked_fill_ cut it out of the graph)
 //   d_target = sum_l dlog[l] context[l];   d_context[l] = p[l] d_weighted + dlog[l] target
 // One workgroup per batch row; logits and dp in LDS from one pass over the context, d_target / d_context from a second.
+// W = floats per load / store: 1 serves every D <= 4096 and is what every width that is a multiple of 4 takes (their
+// results are as they always were); 2 where D % 4 == 2 and every row involved is 8-byte aligned (sdb_pairs).
+__host__ __forceinline__ bool sdb_pairs(const SoftDotBwdArgs& a, const float* d_target) {
+  return ((a.D & 3) == 2) && ((a.ld_row & 1) == 0) && ((a.ld_batch & 1) == 0) &&
+         ((((uintptr_t)a.context) | ((uintptr_t)a.target) | ((uintptr_t)a.d_weighted) | ((uintptr_t)a.d_context) |
+           ((uintptr_t)d_target)) & 7) == 0;
+}
+
+template <int W>
 __global__ __launch_bounds__(64 * SD_WAVES) void softdot_bwd_kernel(SoftDotBwdArgs a, int parts) {
-  extern __shared__ float sl[];          // [L] logits -> p | [L] dp -> dlog | [2 * SD_WAVES] scratch | [parts][D] partial sums
+  // [L] logits -> p | [L] dp -> dlog | [2 * SD_WAVES] scratch | (to 16 bytes) [parts][D] partial sums
+  extern __shared__ __attribute__((aligned(16))) float sl[];
   float* ql = sl + a.L;
   float* red = ql + a.L;
-  float* psum = red + 2 * SD_WAVES;
+  float* psum = sl + sd_carve(2 * a.L + 2 * SD_WAVES);
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* ctx = a.context + (long)b * a.ld_batch;
   const float* tg = a.target + (long)b * a.D;
@@ -378,17 +441,24 @@ __global__ __launch_bounds__(64 * SD_WAVES) void softdot_bwd_kernel(SoftDotBwdAr
   for (int l = wave; l < a.L; l += SD_WAVES) {
     const float* row = ctx + (long)l * a.ld_row;
     float s = 0.f, q = 0.f;
-    for (int d = lane; d < a.D; d += 64) {
-      const float c = row[d];
-      s += c * tg[d];
-      if (dw) q += c * dw[d];
+    for (int d = lane * W; d < a.D; d += 64 * W) {
+      const RowPiece<W> c = RowPiece<W>::ld(row + d), t = RowPiece<W>::ld(tg + d);
+      RowPiece<W> w = c;
+      if (dw) w = RowPiece<W>::ld(dw + d);
+#pragma unroll
+      for (int j = 0; j < W; ++j) {
+        s += c.v[j] * t.v[j];
+        if (dw) q += c.v[j] * w.v[j];
+      }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o, 64); q += __shfl_xor(q, o, 64); }
     if (lane == 0) {
-      if (mk && mk[l]) s = -INFINITY;
+      const bool masked = mk && mk[l];
+      if (masked) s = -INFINITY;
       sl[l] = s;
-      ql[l] = q + ((da && a.output_prob) ? da[l] : 0.f);
+      // a masked key has p == 0 and takes no part: its dp counts as 0 whatever the row holds (0 * NaN must not appear)
+      ql[l] = masked ? 0.f : q + ((da && a.output_prob) ? da[l] : 0.f);
     }
   }
   __syncthreads();
@@ -435,20 +505,33 @@ __global__ __launch_bounds__(64 * SD_WAVES) void softdot_bwd_kernel(SoftDotBwdAr
     ql[l] = g;
   }
   __syncthreads();
-  // thread = (key part, column): d_target partial sums over every parts-th key, d_context written on the way
+  // thread = (key part, column group of W): d_target partial sums over every parts-th key, d_context written on the way.
+  // D > 1024 (parts == 1): the 1024 threads walk the row's columns in steps of 1024 groups.
   const int cols = (64 * SD_WAVES) / parts;
   const int part = tid / cols;
   if (part < parts) {
-    for (int d = tid % cols; d < a.D; d += cols) {
-      float acc = 0.f;
-      const float t = tg[d], w = dw ? dw[d] : 0.f;
+    for (int d = (tid % cols) * W; d < a.D; d += cols * W) {
+      RowPiece<W> acc, w;
+#pragma unroll
+      for (int j = 0; j < W; ++j) acc.v[j] = w.v[j] = 0.f;
+      const RowPiece<W> t = RowPiece<W>::ld(tg + d);
+      if (dw) w = RowPiece<W>::ld(dw + d);
       float* dcx = a.d_context ? a.d_context + ((long)b * a.L) * a.D + d : nullptr;
       for (int l = part; l < a.L; l += parts) {
         const float g = ql[l];
-        if (g != 0.f) acc += g * ctx[(long)l * a.ld_row + d];    // a masked key has g == 0 exactly (and may hold anything)
-        if (dcx) dcx[(long)l * a.D] = sl[l] * w + g * t;
+        if (g != 0.f) {    // a masked key has g == 0 exactly (and may hold anything)
+          const RowPiece<W> c = RowPiece<W>::ld(ctx + (long)l * a.ld_row + d);
+#pragma unroll
+          for (int j = 0; j < W; ++j) acc.v[j] += g * c.v[j];
+        }
+        if (dcx) {
+          RowPiece<W> o;
+#pragma unroll
+          for (int j = 0; j < W; ++j) o.v[j] = sl[l] * w.v[j] + g * t.v[j];
+          o.st(dcx + (long)l * a.D);
+        }
       }
-      psum[(long)part * a.D + d] = acc;
+      acc.st(psum + (long)part * a.D + d);
     }
   }
   __syncthreads();
@@ -466,6 +549,7 @@ __global__ __launch_bounds__(64 * SD_WAVES) void softdot_bwd_kernel(SoftDotBwdAr
 //                       SDB_KEYS keys: d_context rows and a partial d_target                    grid (L / SDB_KEYS, B)
 // the partial d_target sums [B, chunks, D] are added up by the caller (no atomics: the result is reproducible).
 #define SDB_KEYS 32
+template <int W>
 __global__ __launch_bounds__(256) void softdot_bwd_dots(SoftDotBwdArgs a, float* sl_g, float* ql_g) {
   const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l = blockIdx.x * 4 + wave;
@@ -474,21 +558,27 @@ __global__ __launch_bounds__(256) void softdot_bwd_dots(SoftDotBwdArgs a, float*
   const float* tg = a.target + (long)b * a.D;
   const float* dw = a.d_weighted ? a.d_weighted + (long)b * a.D : nullptr;
   float s = 0.f, q = 0.f;
-  for (int d = lane; d < a.D; d += 64) {
-    const float c = row[d];
-    s += c * tg[d];
-    if (dw) q += c * dw[d];
+  for (int d = lane * W; d < a.D; d += 64 * W) {
+    const RowPiece<W> c = RowPiece<W>::ld(row + d), t = RowPiece<W>::ld(tg + d);
+    RowPiece<W> w = c;
+    if (dw) w = RowPiece<W>::ld(dw + d);
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      s += c.v[j] * t.v[j];
+      if (dw) q += c.v[j] * w.v[j];
+    }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o, 64); q += __shfl_xor(q, o, 64); }
   if (lane == 0) {
-    if (a.mask && a.mask[(long)b * a.L + l]) s = -INFINITY;
     if (a.d_attn && a.output_prob) q += a.d_attn[(long)b * a.L + l];
+    if (a.mask && a.mask[(long)b * a.L + l]) { s = -INFINITY; q = 0.f; }   // p == 0: dp counts as 0 whatever the row holds
     sl_g[(long)b * a.L + l] = s;
     ql_g[(long)b * a.L + l] = q;
   }
 }
 
+template <int W>
 __global__ __launch_bounds__(256) void softdot_bwd_apply(SoftDotBwdArgs a, const float* sl_g, const float* ql_g,
                                                          float* dt_part, int chunks) {
   __shared__ float red[8];
@@ -532,15 +622,27 @@ __global__ __launch_bounds__(256) void softdot_bwd_apply(SoftDotBwdArgs a, const
   const float* tg = a.target + (long)b * a.D;
   const float* dw = a.d_weighted ? a.d_weighted + (long)b * a.D : nullptr;
   float* dcx = a.d_context ? a.d_context + ((long)b * a.L + l0) * a.D : nullptr;
-  for (int d = tid; d < a.D; d += 256) {
-    const float t = tg[d], w = dw ? dw[d] : 0.f;
-    float acc = 0.f;
+  for (int d = tid * W; d < a.D; d += 256 * W) {
+    RowPiece<W> acc, w;
+#pragma unroll
+    for (int j = 0; j < W; ++j) acc.v[j] = w.v[j] = 0.f;
+    const RowPiece<W> t = RowPiece<W>::ld(tg + d);
+    if (dw) w = RowPiece<W>::ld(dw + d);
     for (int k = 0; k < nk; ++k) {
       const float g = gk[k];
-      if (g != 0.f) acc += g * ctx[(long)k * a.ld_row + d];
-      if (dcx) dcx[(long)k * a.D + d] = pk[k] * w + g * t;
+      if (g != 0.f) {
+        const RowPiece<W> c = RowPiece<W>::ld(ctx + (long)k * a.ld_row + d);
+#pragma unroll
+        for (int j = 0; j < W; ++j) acc.v[j] += g * c.v[j];
+      }
+      if (dcx) {
+        RowPiece<W> o;
+#pragma unroll
+        for (int j = 0; j < W; ++j) o.v[j] = pk[k] * w.v[j] + g * t.v[j];
+        o.st(dcx + (long)k * a.D + d);
+      }
     }
-    dt_part[((long)b * chunks + chunk) * a.D + d] = acc;
+    acc.st(dt_part + ((long)b * chunks + chunk) * a.D + d);
   }
 }
 
@@ -556,10 +658,15 @@ int vt_softdot_bwd_split_dispatch(const SoftDotBwdArgs& a, float* ws, hipStream_
   const int chunks = (a.L + SDB_KEYS - 1) / SDB_KEYS;
   float* sl = ws;
   float* ql = ws + (long)a.B * a.L;
-  float* part = ql + (long)a.B * a.L;
-  hipLaunchKernelGGL(softdot_bwd_dots, dim3((a.L + 3) / 4, a.B), dim3(256), 0, stream, a, sl, ql);
-  hipLaunchKernelGGL(softdot_bwd_apply, dim3(chunks, a.B), dim3(256), 0, stream, a, (const float*)sl, (const float*)ql, part,
-                     chunks);
+  float* part = ql + (long)a.B * a.L;   // 2 * B * L floats in: 8-byte aligned when ws is (its rows are D floats, D even then)
+  const dim3 gd((a.L + 3) / 4, a.B), ga(chunks, a.B);
+  if (sdb_pairs(a, part)) {
+    hipLaunchKernelGGL(softdot_bwd_dots<2>, gd, dim3(256), 0, stream, a, sl, ql);
+    hipLaunchKernelGGL(softdot_bwd_apply<2>, ga, dim3(256), 0, stream, a, (const float*)sl, (const float*)ql, part, chunks);
+  } else {
+    hipLaunchKernelGGL(softdot_bwd_dots<1>, gd, dim3(256), 0, stream, a, sl, ql);
+    hipLaunchKernelGGL(softdot_bwd_apply<1>, ga, dim3(256), 0, stream, a, (const float*)sl, (const float*)ql, part, chunks);
+  }
   return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
 }
 
@@ -567,16 +674,17 @@ int vt_softdot_bwd_dispatch(const SoftDotBwdArgs& a, hipStream_t stream) {
   if (!a.target || !a.context || !a.d_target) return VT_ERR_NULL;
   if (!a.d_weighted && !a.d_attn) return VT_ERR_NULL;
   if (a.B <= 0 || a.L <= 0 || a.D <= 0 || a.L > 8192) return VT_ERR_BAD_SHAPE;
-  int parts = (64 * SD_WAVES) / a.D;                 // key parts when a row has fewer columns than the workgroup threads
-  if (parts > 8) parts = 8;
-  if (parts > a.L) parts = a.L;
-  if (parts < 1) parts = 1;
-  const size_t lds = (2 * (size_t)a.L + 2 * SD_WAVES + (size_t)parts * a.D) * sizeof(float);
+  const bool pairs = sdb_pairs(a, a.d_target);
+  // key parts when a row has fewer column groups than the workgroup has threads; 1 from D > 1024 (512 pairs) on, where the
+  // threads walk the columns in steps of 1024 groups
+  const int parts = sd_parts(sd_groups(a.D, pairs ? 2 : 1), a.L);
+  const size_t lds = ((size_t)sd_carve(2 * a.L + 2 * SD_WAVES) + (size_t)parts * a.D) * sizeof(float);
   if (lds > 160 * 1024) return VT_ERR_BAD_SHAPE;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)softdot_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+  const void* fn = pairs ? (const void*)softdot_bwd_kernel<2> : (const void*)softdot_bwd_kernel<1>;
+  if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return VT_ERR_HIP;
-  hipLaunchKernelGGL(softdot_bwd_kernel, dim3(a.B), dim3(64 * SD_WAVES), lds, stream, a, parts);
+  if (pairs) hipLaunchKernelGGL(softdot_bwd_kernel<2>, dim3(a.B), dim3(64 * SD_WAVES), lds, stream, a, parts);
+  else hipLaunchKernelGGL(softdot_bwd_kernel<1>, dim3(a.B), dim3(64 * SD_WAVES), lds, stream, a, parts);
   return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
 }
 
@@ -587,6 +695,11 @@ int vt_softdot_bwd_dispatch(const SoftDotBwdArgs& a, hipStream_t stream) {
 // its 4 waves take every fourth 32-wide K-step (W rows on the MFMA A port, the activations converted to bf16 on the B
 // port, both straight from L2), partial sums meet in LDS.  Also folds the K-concatenation (torch.cat of the weighted
 // context and the query, :354) and the bf16 packing that the big kernel needs as separate launches.
+// Any K0 >= 1, K1 >= 0, N and row strides: a lane's 4-column group of the virtual [x0 | x1] row is read by address
+// (load4_cat: 16-, 8- or 4-byte loads, element by element across the seam and at the end of the row), so nothing outside
+// columns [0, K0) / [0, K1) of a row is touched.  GRID = K0, K1 and the strides multiples of 4 on 16-byte aligned bases (every
+// shipped width): the loop those shapes always ran, one unconditional 16-byte load per group, no look at the address.
+template <bool GRID>
 __global__ __launch_bounds__(256) void skinny_linear_kernel(SkinnyArgs a) {
   __shared__ f32x4 part[4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -608,7 +721,11 @@ __global__ __launch_bounds__(256) void skinny_linear_kernel(SkinnyArgs a) {
     for (int h = 0; h < 2; ++h) {
       const int c = kk + 4 * h;
       v[h] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (xok && c < K) v[h] = c < a.K0 ? *(const f32x4*)(p0 + c) : *(const f32x4*)(p1 + (c - a.K0));   // K0, K % 4 == 0
+      if (GRID) {
+        if (xok && c < K) v[h] = c < a.K0 ? *(const f32x4*)(p0 + c) : *(const f32x4*)(p1 + (c - a.K0));
+      } else if (xok) {
+        v[h] = load4_cat(p0, a.K0, p1, K, c);
+      }
     }
     u32x4 xb;
     xb[0] = pack_bf16x2(v[0][0], v[0][1]); xb[1] = pack_bf16x2(v[0][2], v[0][3]);
@@ -631,10 +748,13 @@ __global__ __launch_bounds__(256) void skinny_linear_kernel(SkinnyArgs a) {
 int vt_skinny_linear_dispatch(const SkinnyArgs& a, hipStream_t stream) {
   if (!a.x0 || !a.w || !a.out) return VT_ERR_NULL;
   if (a.M <= 0 || a.N <= 0 || a.K0 <= 0 || a.K1 < 0 || (a.K1 > 0 && !a.x1)) return VT_ERR_BAD_SHAPE;
-  if ((a.K0 & 3) || (a.K1 & 3) || (a.Kpad & 31) || a.Kpad < a.K0 + a.K1 || a.ldw < a.Kpad) return VT_ERR_BAD_SHAPE;
-  if ((a.ld0 & 3) || (a.K1 && (a.ld1 & 3)) || (a.ldw & 7)) return VT_ERR_BAD_ALIGN;
-  if ((((uintptr_t)a.x0) | ((uintptr_t)a.x1) | ((uintptr_t)a.w)) & 15) return VT_ERR_BAD_ALIGN;
+  if ((a.Kpad & 31) || a.Kpad < a.K0 + a.K1 || a.ldw < a.Kpad) return VT_ERR_BAD_SHAPE;
+  if ((a.ldw & 7) || (((uintptr_t)a.w) & 15)) return VT_ERR_BAD_ALIGN;
+  if ((((uintptr_t)a.x0) | ((uintptr_t)a.x1)) & 3) return VT_ERR_BAD_ALIGN;
   if (a.act != 0 && a.act != 2) return VT_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(skinny_linear_kernel, dim3((a.N + 15) / 16, (a.M + 15) / 16), dim3(256), 0, stream, a);
+  const bool grid = !((a.K0 | a.K1 | a.ld0 | (a.K1 ? a.ld1 : 0)) & 3) && !((((uintptr_t)a.x0) | ((uintptr_t)a.x1)) & 15);
+  const dim3 blocks((a.N + 15) / 16, (a.M + 15) / 16);
+  if (grid) hipLaunchKernelGGL(skinny_linear_kernel<true>, blocks, dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL(skinny_linear_kernel<false>, blocks, dim3(256), 0, stream, a);
   return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_HIP;
 }

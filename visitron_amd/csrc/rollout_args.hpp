@@ -47,8 +47,8 @@ struct SoftDotBwdArgs {
 };
 
 struct SoftDotArgs {
-  const float* target;          // [B, D]
-  const float* context;         // [B, L, D], row stride ld_row, batch stride ld_batch (elements)
+  const float* target;          // [B, D], 1 <= D <= 4096
+  const float* context;         // [B, L, D], row stride ld_row, batch stride ld_batch (elements, any)
   long ld_batch, ld_row;
   const unsigned char* mask;    // [B, L] (nonzero = masked) or null
   float* weighted;              // [B, D] or null
@@ -57,8 +57,8 @@ struct SoftDotArgs {
 };
 
 struct SkinnyArgs {
-  const float* x0; long ld0; int K0;   // [M, K0] fp32
-  const float* x1; long ld1; int K1;   // [M, K1] fp32 or null: K-concatenated behind x0 (K0 % 4 == 0)
+  const float* x0; long ld0; int K0;   // [M, K0] fp32, any K0 >= 1 and row stride
+  const float* x1; long ld1; int K1;   // [M, K1] fp32 or null: K-concatenated behind x0 (any K1 >= 0; a group of 4 may straddle)
   const bf16_t* w; long ldw;           // [N, Kpad] bf16, zero past K0 + K1; Kpad % 32 == 0
   const float* bias;                   // [N] or null
   float* out; long ldo;                // [M, N] fp32

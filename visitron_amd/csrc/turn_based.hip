@@ -3,6 +3,7 @@
 //   * the action head around the step: blocked logits, cross entropy with ignore_index, next action (teacher / argmax /
 //     sample), and its gradient
 #include "dispatch.hpp"
+#include "row_loads.hpp"
 
 __device__ __forceinline__ float tb_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ __forceinline__ float tb_tanh(float x) {
@@ -22,31 +23,7 @@ __device__ __forceinline__ float tb_tanh(float x) {
 // source and its address is 16-byte aligned, with two 8-byte loads when 8-byte aligned, and element by element
 // otherwise; no load touches an element outside columns [0, E) / [0, F) of its row.
 
-// 4 consecutive columns c .. c+3 of the virtual concatenated row
-__device__ __forceinline__ f32x4 tb_load4(const float* ep, int E, const float* fp, int K, int c) {
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (c >= K) return v;
-  const float* p = nullptr;
-  if (c + 4 <= E) p = ep ? ep + c : nullptr;
-  else if (c >= E && c + 4 <= K) p = fp + (c - E);
-  if (p) {
-    const uintptr_t ad = (uintptr_t)p;
-    if ((ad & 15) == 0) return *(const f32x4*)p;
-    if ((ad & 7) == 0) {
-      const f32x2 lo = *(const f32x2*)p, hi = *(const f32x2*)(p + 2);
-      return (f32x4){lo[0], lo[1], hi[0], hi[1]};
-    }
-    return (f32x4){p[0], p[1], p[2], p[3]};
-  }
-  if (c + 4 <= E) return v;   // an embedding row that counts as zero (id out of range)
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {   // the group straddles the seam between the two sources, or the end of the row
-    const int cc = c + j;
-    if (cc < E) v[j] = ep ? ep[cc] : 0.f;
-    else if (cc < K) v[j] = fp[cc - E];
-  }
-  return v;
-}
+// (load4_cat, row_loads.hpp: 4 consecutive columns of the virtual concatenated row)
 
 __global__ __launch_bounds__(256) void tb_lstm_cell_kernel(TbCellArgs a) {
   __shared__ f32x4 part[4][4][64];   // [wave][gate][lane]
@@ -82,7 +59,7 @@ __global__ __launch_bounds__(256) void tb_lstm_cell_kernel(TbCellArgs a) {
     long gstride;
     if (s < nx) {
       const int c = s * 32 + kl;
-      if (bvalid) { x0 = tb_load4(ep, E, fp, K, c); x1 = tb_load4(ep, E, fp, K, c + 4); }
+      if (bvalid) { x0 = load4_cat(ep, E, fp, K, c); x1 = load4_cat(ep, E, fp, K, c + 4); }
       wp = wih + s * 32;
       gstride = (long)hs * a.ldw;
     } else {

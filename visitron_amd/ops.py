@@ -1462,8 +1462,11 @@ def lstm_step(xproj, h_prev, h_out, c, w_hh, t=0, lengths=None, seq_out=None):
 
 
 def softdot_attention(target, context, mask=None, want_weighted=True, want_attn=True, output_prob=True):
-    """SoftDotAttention after linear_in: target fp32 [B,D], context fp32 [B,L,D] (last dim contiguous), mask
-    bool/uint8 [B,L] (nonzero = masked) -> (weighted fp32 [B,D] | None, attn fp32 [B,L] | None)."""
+    """SoftDotAttention after linear_in: target fp32 [B,D], context fp32 [B,L,D] (last dim contiguous, any row and batch
+    stride), mask bool/uint8 [B,L] (nonzero = masked) -> (weighted fp32 [B,D] | None, attn fp32 [B,L] | None).
+    Any 1 <= D <= 4096: 16-byte loads where D and the strides are multiples of 4 on 16-byte aligned bases, 8-byte loads where
+    D % 4 == 2 on even strides and 8-byte aligned bases (2058), element loads otherwise; nothing outside a row's D columns is
+    read.  A masked key is never multiplied into the weighted sum; a row with every key masked is NaN."""
     _require_hip(target, context, mask)
     B, L, D = context.shape
     assert target.dtype == torch.float32 and target.shape == (B, D) and target.is_contiguous()
@@ -1550,8 +1553,9 @@ def lstm_sequence(xproj, h2, c, w_hh, T, lengths=None, seq_out=None, reverse=Fal
 
 
 def skinny_linear(x0, w_pad, bias=None, x1=None, act=ACT_NONE):
-    """act([x0 | x1] @ W.T + bias) in fp32 for a handful of rows: x0 [M,K0], x1 [M,K1] fp32 (row strides allowed, K0 and
-    K1 multiples of 4), w_pad bf16 [N, Kpad] zero-padded past K0 + K1 (Kpad a multiple of 32)."""
+    """act([x0 | x1] @ W.T + bias) in fp32 for a handful of rows: x0 [M,K0], x1 [M,K1] fp32 (any widths K0 >= 1, K1 >= 0,
+    any row strides: the rows are read by address, a 4-column group may straddle the two), any N, w_pad bf16 [N, Kpad]
+    zero-padded past K0 + K1 (Kpad a multiple of 32, row stride a multiple of 8)."""
     _require_hip(x0, x1, w_pad, bias)
     assert x0.dtype == torch.float32 and x0.dim() == 2 and x0.stride(1) == 1
     M, K0 = x0.shape

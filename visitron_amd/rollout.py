@@ -7,7 +7,9 @@ Drop-ins for tasks/viewpoint_select/agent_models.py: `OscarEncoder` (:192-310), 
 `lstm.weight_ih_l0`, `feat_att_layer.linear_in.weight`, ...), argument meaning and return values.  `nn.LSTM` /
 `nn.LSTMCell` are kept as parameter containers only; their arithmetic runs in vt_lstm_sequence_f32 / vt_lstm_step_f32,
 the dot attentions in vt_softdot_attention_f32, every dense projection in the NT GEMM.  No CPU fallback.  nn.Dropout
-(the modules' `drop`) is a torch elementwise op on the device in training mode.
+(the modules' `drop`) is a torch elementwise op on the device in training mode.  Feature widths are free up to 4096 (the
+reference's default 2058 included); where embedding + feature width is no multiple of 4 the decoder's cell is the fused
+vt_turn_lstm_cell_f32 (`fused_cell`).
 """
 import torch
 import torch.nn as nn
@@ -59,12 +61,12 @@ def _f32c(x):
 
 
 def _dense(x_parts, w_pad, bias=None, act=ACT_NONE):
-    """act([x_parts...] @ W.T + bias) in fp32: x_parts = one or two fp32 [M, d] tensors K-concatenated into the bf16
-    operand (vt_pack_concat_bf16), W pre-padded bf16 [N, kpad]."""
+    """act([x_parts...] @ W.T + bias) in fp32: x_parts = one or two fp32 [M, d] tensors of any width, W pre-padded bf16
+    [N, kpad].  Up to SKINNY_ROWS rows: one vt_skinny_linear_f32 launch; more: K-concatenated into the bf16 operand
+    (vt_pack_concat_bf16) for the tiled GEMM."""
     s0 = _f32c(x_parts[0])
     s1 = _f32c(x_parts[1]) if len(x_parts) > 1 else None
-    if s0.shape[0] <= SKINNY_ROWS and s0.shape[1] % 4 == 0 and (s1 is None or s1.shape[1] % 4 == 0) \
-            and act in (ACT_NONE, ACT_TANH):
+    if s0.shape[0] <= SKINNY_ROWS and act in (ACT_NONE, ACT_TANH):
         return ops.skinny_linear(s0, w_pad, bias, s1, act)   # a few rows: one launch, no packing pass
     a = ops.pack_concat(s0, s1, w_pad.shape[1])
     N = w_pad.shape[0]
@@ -168,8 +170,16 @@ class _DecoderStepGraph(object):
         return tuple(t.view(shp) for t, shp in zip(out.split(self.sizes), self.shapes))
 
 
+def fused_cell(embedding_size, feature_size):
+    """The decoder's cell route.  False: the input projection as a dense launch, then vt_lstm_step_f32 -- every input width
+    that is a multiple of 4 (64 + 2052, 64 + 132: the shipped widths, unchanged).  True: [action_embeds | attn_feat] through
+    vt_turn_lstm_cell_f32, which reads both blocks by address and carries the projection itself -- every other width (the
+    reference's default 64 + 2058)."""
+    return (embedding_size + feature_size) % 4 != 0
+
+
 class AttnDecoderLSTM(nn.Module):
-    """agent_models.py:360-428: one decoder step (3 dot attentions around an LSTM cell)."""
+    """agent_models.py:360-428: one decoder step (3 dot attentions around an LSTM cell).  Any feature_size."""
 
     def __init__(self, angle_feat_size, embedding_size, hidden_size, dropout_ratio, feature_size=2048 + 4):
         super().__init__()
@@ -210,8 +220,12 @@ class AttnDecoderLSTM(nn.Module):
         # the query of each of the three attentions, never on the state the cell carries forward
         emb_a = self.drop(ra.dense(action, emb.weight, emb.bias, ACT_TANH, packs[0]))
         seen, _ = self.feat_att_layer(self.drop(prev_h1), feature, output_tilde=False)
-        h_1, c_1 = ra.lstm_cell(torch.cat((emb_a, seen), 1), prev_h1, c_0, cell.weight_ih, cell.weight_hh, cell.bias_ih,
-                                cell.bias_hh, packs[1])
+        if fused_cell(self.embedding_size, self.feature_size):
+            h_1, c_1 = ra.fused_lstm_cell(emb_a, seen, prev_h1, c_0, cell.weight_ih, cell.weight_hh, cell.bias_ih,
+                                          cell.bias_hh, packs[1])
+        else:
+            h_1, c_1 = ra.lstm_cell(torch.cat((emb_a, seen), 1), prev_h1, c_0, cell.weight_ih, cell.weight_hh, cell.bias_ih,
+                                    cell.bias_hh, packs[1])
         h_att, _ = self.attention_layer(self.drop(h_1), ctx, ctx_mask)
         _, scores = self.candidate_att_layer(self.drop(h_att), cand_feat, output_prob=False)
         return h_1, c_1, scores, h_att
@@ -233,15 +247,18 @@ class AttnDecoderLSTM(nn.Module):
         return self._step(action, feature, cand_feat, prev_h1, c_0, ctx, ctx_mask)
 
     def _step(self, action, feature, cand_feat, prev_h1, c_0, ctx, ctx_mask):
-        """agent_models.py:406-425, inference: ten launches."""
+        """agent_models.py:406-425, inference: ten launches (nine with the fused cell)."""
         w = self._weights()
         action_embeds = _dense((action,), w["w_emb"], w["b_emb"], act=ACT_TANH)                 # :406
         attn_feat, _ = self.feat_att_layer.attend(prev_h1, feature, None, True, False, True)      # :411-412
-        xproj = _dense((action_embeds, attn_feat), w["w_ih"], w["b"])                             # :414-417, x half
         hp = _f32c(prev_h1)
-        h_1 = torch.empty_like(hp)
-        c_1 = _f32c(c_0).clone()
-        ops.lstm_step(xproj, hp, h_1, c_1, w["w_hh"])                                             # :417, h half + gates
+        if fused_cell(self.embedding_size, self.feature_size):                                    # :414-417 in one launch
+            h_1, c_1, _ = ops.turn_lstm_cell(action_embeds, attn_feat, hp, _f32c(c_0), w["w_ih"], w["w_hh"], w["b"])
+        else:
+            xproj = _dense((action_embeds, attn_feat), w["w_ih"], w["b"])                         # :414-417, x half
+            h_1 = torch.empty_like(hp)
+            c_1 = _f32c(c_0).clone()
+            ops.lstm_step(xproj, hp, h_1, c_1, w["w_hh"])                                         # :417, h half + gates
         h_tilde, _ = self.attention_layer(h_1, ctx, ctx_mask)                                     # :419-420
         _, logit = self.candidate_att_layer.attend(h_tilde, cand_feat, None, False, True, False)  # :423-425
         return h_1, c_1, logit, h_tilde

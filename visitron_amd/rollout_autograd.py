@@ -47,11 +47,21 @@ def _bf16_rows(x, mult=8):
 
 
 def _wgrad_problem(dy16, x16, N, K):
-    if K % 4:
-        raise NotImplementedError("weight gradients are served for input widths that are multiples of 4 (got %d)" % K)
-    dw = torch.empty((N, K), dtype=torch.float32, device=dy16.device)
-    db = torch.empty((N,), dtype=torch.float32, device=dy16.device)
-    return dict(dy=dy16[:, :N], x=x16[:, :K], dw=dw, db=db)
+    """One vt_wgrad_bf16 problem for dW [N, K] = dy^T x and db [N] from the _bf16_rows operands (zero columns up to a
+    multiple of 8).  The kernel takes input widths in multiples of 4: such a K is served at its own size.  Any other K runs
+    at the operands' padded widths -- dw [Np, Kp] and db [Np] are whole buffers, the zero columns give zero rows / columns --
+    and the caller gets the [:N, :K] / [:N] views (`dw`, `db` of the returned dict either way; `run` is what is launched)."""
+    dev = dy16.device
+    if K % 4 == 0:
+        dw = torch.empty((N, K), dtype=torch.float32, device=dev)
+        db = torch.empty((N,), dtype=torch.float32, device=dev)
+        run = dict(dy=dy16[:, :N], x=x16[:, :K], dw=dw, db=db)
+        return dict(run=run, dw=dw, db=db)
+    Np, Kp = dy16.shape[1], x16.shape[1]
+    assert Np % 8 == 0 and Kp % 8 == 0 and Np >= N and Kp >= K
+    dwp = torch.empty((Np, Kp), dtype=torch.float32, device=dev)
+    dbp = torch.empty((Np,), dtype=torch.float32, device=dev)
+    return dict(run=dict(dy=dy16, x=x16, dw=dwp, db=dbp), dw=dwp[:N, :K], db=dbp[:N])
 
 
 class _Dense(torch.autograd.Function):
@@ -83,7 +93,7 @@ class _Dense(torch.autograd.Function):
             dx = dx if dx.shape[1] == K else dx[:, :K]
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
             pr = _wgrad_problem(_bf16_rows(dz), _bf16_rows(x), N, K)
-            ops.wgrad([pr], M)
+            ops.wgrad([pr["run"]], M)
             dw, db = pr["dw"], (pr["db"] if ctx.has_bias else None)
         return dx, dw, db, None, None
 
@@ -124,8 +134,8 @@ def _lstm_weight_grads(dg16, x16, in_dim, h16, hs, M, needs):
     G = 4 * hs
     p_ih = _wgrad_problem(dg16, x16, G, in_dim)
     p_hh = _wgrad_problem(dg16, h16, G, hs)
-    p_hh["db"] = None
-    ops.wgrad([p_ih, p_hh], M)
+    p_hh["run"]["db"] = None
+    ops.wgrad([p_ih["run"], p_hh["run"]], M)
     return p_ih["dw"], p_hh["dw"], p_ih["db"]
 
 
@@ -169,6 +179,15 @@ def lstm_cell(x, h_prev, c_prev, w_ih, w_hh, b_ih, b_hh, packs):
     """nn.LSTMCell(x, (h_prev, c_prev)) -> (h_1, c_1) as an autograd node; packs = (W_ih padded, W_ih^T padded, W_hh bf16,
     W_hh^T bf16)."""
     return _LSTMCell.apply(x, h_prev, c_prev, w_ih, w_hh, b_ih, b_hh, packs)
+
+
+def fused_lstm_cell(x_emb, feature, h_prev, c_prev, w_ih, w_hh, b_ih, b_hh, packs):
+    """nn.LSTMCell(cat(x_emb, feature), (h_prev, c_prev)) -> (h_1, c_1) as ONE autograd node for the two blocks as they are
+    (any widths; no concatenated copy): the turn-based decoder's cell node (turn_based._TurnCell: vt_turn_lstm_cell_f32
+    forward with the saves, the wgrad operand padded to 8 columns and dW_ih sliced back).  packs as for lstm_cell."""
+    from .turn_based import _TurnCell   # (turn_based imports this module)
+
+    return _TurnCell.apply(x_emb, feature, h_prev, c_prev, w_ih, w_hh, b_ih, b_hh, packs)
 
 
 class _LSTMSequence(torch.autograd.Function):
