@@ -610,6 +610,33 @@ int vt_obs_gather_f32(const float* store, int64_t N, int V, int D, const float* 
 int vt_obs_gather_view_f32(const float* store, int64_t N, int V, int D, const int32_t* rows, int B, float* out,
                            int64_t ld_out, int32_t* err_flag, vt_stream_t stream);
 
+/* ---- pretraining's region features from a device region store (ABI 21): data_loader_pretrain.py:615-634, 654-712 ---------------
+ *
+ * store [N, V = 36, P, ld] contiguous, 16-byte aligned, fp32 (store_bf16 == 0) or bf16 (store_bf16 == 1), ld = round_up(D, 8):
+ * up to P region rows of every view of N viewpoints; counts uint8 [N, V] = how many of a view's P rows exist.  rows int32
+ * [B][2] = slot, current_view_index on the device.  loc_table fp32 [36, 36, 128] (16-byte aligned) = _static_loc_embeddings.
+ * Item b's regions are the stored rows of views 0..35 in order, counts[slot_b, v] of view v: n_b rows.  Output row r < R
+ * is region start_b + r with start_b = max(n_b - R, 0) (more than R keep the LAST R), or zero where start_b + r >= n_b:
+ *   vt_region_gather_f32:       feats_out fp32 [B, R, D] = the stored row (a bf16 store's value widened)
+ *                               loc_out   fp32 [B, R, 128] (16-byte aligned) = loc_table[current_view_b][the row's view]
+ *   vt_region_gather_pack_bf16: packed_out bf16 [B * R, kpad] (16-byte aligned; kpad % 8 == 0, kpad >= D + 128)
+ *                               = bf16([feature row | location row | zeros]): what vt_pack_concat_bf16 makes of the two
+ *                               tensors above, from the store in one pass; every 16-byte piece is written exactly once
+ * and, by both, the [B, T + R] int64 tensors: labels_out = [text_labels | -1], mask_out = [text_mask != 0 | row valid],
+ * token_labels_out = [text_token_classes | -1] (both null, or both given).
+ * A slot outside [0, N), a current view outside [0, 36) or a count above P: that item's region rows are zeros with mask 0
+ * and *err_flag (optional) is set to 1; nothing outside store, counts, loc_table, rows and the text tensors is read. */
+int vt_region_gather_f32(const void* store, int store_bf16, int64_t N, int V, int P, int D, const uint8_t* counts,
+                         const float* loc_table, const int32_t* rows, const int64_t* text_labels, const int64_t* text_mask,
+                         const int64_t* text_token_classes, int B, int T, int R, float* feats_out, float* loc_out,
+                         int64_t* labels_out, int64_t* mask_out, int64_t* token_labels_out, int32_t* err_flag,
+                         vt_stream_t stream);
+int vt_region_gather_pack_bf16(const void* store, int store_bf16, int64_t N, int V, int P, int D, const uint8_t* counts,
+                               const float* loc_table, const int32_t* rows, const int64_t* text_labels,
+                               const int64_t* text_mask, const int64_t* text_token_classes, int B, int T, int R,
+                               void* packed_out, int kpad, int64_t* labels_out, int64_t* mask_out,
+                               int64_t* token_labels_out, int32_t* err_flag, vt_stream_t stream);
+
 /* out[c, r] = in[r, c] (bf16; R, C multiples of 8): refreshes the transposed weight copies (W^T of every nn.Linear on the
  * path, oscar/modeling_bert.py:43-45,94,119,120) that the
  * dgrad GEMMs consume (vt_layer_weights_t). */

@@ -5,6 +5,7 @@ Public surface = the reference's module API for this path (see ``visitron_amd.mo
 ``BertConfig``, ``MODEL_CLASS``; ``set_precision(model, "fp32")`` selects the fp32 parity kernels (default: bf16);
 ``check_errors()`` waits for the asynchronous error flags of the calls issued so far (ids outside an embedding table);
 ``set_deterministic(True)`` / ``is_deterministic()``: training steps that agree bit for bit from run to run.
+``FeatureStore`` / ``RegionStore``: the rollout's observation tensors and pretraining's region features served from the device.
 Arithmetic runs in ``lib/libvisitron_hip.so`` (C ABI in
 ``include/visitron_hip.h``); there is no CPU fallback.
 """
@@ -28,4 +29,8 @@ def __getattr__(name):  # lazy: importing the package must not require torch+HIP
         from . import observations
 
         return getattr(observations, name)
+    if name == "RegionStore":   # pretraining's region features from a device region store
+        from . import regions
+
+        return regions.RegionStore
     raise AttributeError(name)

@@ -21,7 +21,7 @@ const char* vt_error_string(int code) {
   }
 }
 
-int vt_abi_version(void) { return 20; }
+int vt_abi_version(void) { return 21; }
 
 // deterministic training mode (common.hpp): one word for the process, read by every dispatch at launch time
 void vt_set_deterministic(int on) { vt_deterministic_word().store(on ? 1 : 0, std::memory_order_relaxed); }
@@ -428,6 +428,44 @@ int vt_obs_gather_view_f32(const float* store, int64_t N, int V, int D, const in
   a.store = store; a.N = N; a.V = V; a.D = D; a.rows = (const int*)rows; a.B = B; a.out = out; a.ld_out = ld_out;
   a.err = (int*)err_flag;
   return vt_obs_gather_view_dispatch(a, (hipStream_t)stream);
+}
+
+static RegionGatherArgs region_args(const void* store, int store_bf16, int64_t N, int V, int P, int D, const uint8_t* counts,
+                                    const float* loc_table, const int32_t* rows, const int64_t* text_labels,
+                                    const int64_t* text_mask, const int64_t* text_token_classes, int B, int T, int R,
+                                    int64_t* labels_out, int64_t* mask_out, int64_t* token_labels_out, int32_t* err_flag) {
+  RegionGatherArgs a;
+  a.store = store; a.store_bf16 = store_bf16; a.N = N; a.V = V; a.P = P; a.D = D; a.counts = counts; a.loc_table = loc_table;
+  a.rows = (const int*)rows; a.text_labels = (const long*)text_labels; a.text_mask = (const long*)text_mask;
+  a.text_token_classes = (const long*)text_token_classes; a.B = B; a.T = T; a.R = R;
+  a.feats = nullptr; a.loc = nullptr; a.packed = nullptr; a.kpad = 0;
+  a.labels = (long*)labels_out; a.mask = (long*)mask_out; a.token_labels = (long*)token_labels_out; a.err = (int*)err_flag;
+  return a;
+}
+
+int vt_region_gather_f32(const void* store, int store_bf16, int64_t N, int V, int P, int D, const uint8_t* counts,
+                         const float* loc_table, const int32_t* rows, const int64_t* text_labels, const int64_t* text_mask,
+                         const int64_t* text_token_classes, int B, int T, int R, float* feats_out, float* loc_out,
+                         int64_t* labels_out, int64_t* mask_out, int64_t* token_labels_out, int32_t* err_flag,
+                         vt_stream_t stream) {
+  RegionGatherArgs a = region_args(store, store_bf16, N, V, P, D, counts, loc_table, rows, text_labels, text_mask,
+                                   text_token_classes, B, T, R, labels_out, mask_out, token_labels_out, err_flag);
+  if (R > 0 && (!feats_out || !loc_out)) return VT_ERR_NULL;
+  a.feats = feats_out; a.loc = loc_out;
+  return vt_region_gather_dispatch(a, (hipStream_t)stream);
+}
+
+int vt_region_gather_pack_bf16(const void* store, int store_bf16, int64_t N, int V, int P, int D, const uint8_t* counts,
+                               const float* loc_table, const int32_t* rows, const int64_t* text_labels,
+                               const int64_t* text_mask, const int64_t* text_token_classes, int B, int T, int R,
+                               void* packed_out, int kpad, int64_t* labels_out, int64_t* mask_out,
+                               int64_t* token_labels_out, int32_t* err_flag, vt_stream_t stream) {
+  RegionGatherArgs a = region_args(store, store_bf16, N, V, P, D, counts, loc_table, rows, text_labels, text_mask,
+                                   text_token_classes, B, T, R, labels_out, mask_out, token_labels_out, err_flag);
+  if (R > 0 && !packed_out) return VT_ERR_NULL;
+  if (kpad < 8) return VT_ERR_BAD_SHAPE;
+  a.packed = packed_out; a.kpad = kpad;
+  return vt_region_gather_dispatch(a, (hipStream_t)stream);
 }
 
 int vt_transpose_bf16(const void* in, int64_t ldi, void* out, int64_t ldo, int R, int C, vt_stream_t stream) {

@@ -203,6 +203,21 @@ int vt_tb_action_head_bwd_dispatch(const TbHeadBwdArgs& a, hipStream_t stream);
 int vt_obs_gather_dispatch(const ObsGatherArgs& a, hipStream_t stream);
 int vt_obs_gather_view_dispatch(const ObsViewArgs& a, hipStream_t stream);
 
+// ---- regions.hip: pretraining's region rows gathered from the device region store
+struct RegionGatherArgs {
+  const void* store; int store_bf16; long N; int V, P, D;   // [N, V, P, round_up(D, 8)] fp32 or bf16
+  const unsigned char* counts;               // [N, V] rows present per view
+  const float* loc_table;                    // [36, 36, 128]
+  const int* rows;                           // [B][2] slot, current view
+  const long* text_labels; const long* text_mask; const long* text_token_classes;   // [B, T] (token classes may be null)
+  int B, T, R;
+  float* feats; float* loc;                  // the unpacked form: [B, R, D], [B, R, 128] ...
+  void* packed; int kpad;                    // ... or the packed one: bf16 [B * R, kpad]
+  long* labels; long* mask; long* token_labels;   // [B, T + R] (token labels may be null)
+  int* err;                                  // device flag raised by a bad index, or null
+};
+int vt_region_gather_dispatch(const RegionGatherArgs& a, hipStream_t stream);
+
 // ---- layernorm.hip: the bf16 engine's LayerNorm and embedding LayerNorm, forward and backward
 int vt_layernorm_dispatch(const void* x, long ldx, void* y, long ldy, const float* gamma, const float* beta,
                           float* mean, float* rstd, int M, int H, float eps, int grp_rows, int grp_stride,

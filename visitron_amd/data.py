@@ -1,8 +1,9 @@
 """Pretrain input preparation on the device: what PretrainDataset does per item in Python
 before the hot path (tasks/viewpoint_select/data_loader_pretrain.py:25-49, 549-613, 615-712), batched as tensor ops so
-it keeps up with the encoder.  Storage (LMDB features, JSON dialogs, tokenizer) stays out of scope: the callers hand
-over token ids, per-region view ids and features; this module does the masking, the location-embedding lookup, the
-region padding / truncation and the label / attention-mask assembly.
+it keeps up with the encoder.  Storage (JSON dialogs, tokenizer) stays out of scope: the callers hand over token ids,
+per-region view ids and features; this module does the masking, the location-embedding lookup, the region padding /
+truncation and the label / attention-mask assembly.  The region features themselves (the LMDB records) can live on the
+device: regions.RegionStore holds them and its pretrain_batch does assemble_batch's work straight from the store.
 
 Random draws are taken from a torch.Generator (or passed in, which is how the tests pin this against
 oracle/data.py): the reference's stream of torch.bernoulli / torch.randint calls per item is not reproduced, the

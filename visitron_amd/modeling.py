@@ -1040,12 +1040,15 @@ class BertImgModelwithLocationEmbeds(BertPreTrainedModel):
         return self._img_pack
 
     def run_trunk(self, input_ids, token_type_ids=None, attention_mask=None, position_ids=None, head_mask=None,
-                  img_feats=None, img_location_embeddings=None, encoder_history_states=None, keep=None):
+                  img_feats=None, img_location_embeddings=None, encoder_history_states=None, keep=None, img_packed=None,
+                  img_rows=None):
         """Internal: returns (per-layer bf16 outputs list, pooled fp32 [B,H], embedding bf16, B, S).
         keep (bool [B,S], optional): the caller only reads the positions marked True and vouches that the others are the
         masked ones (OscarEncoder: the padding behind each instruction) -- the encoder then runs on those rows alone
         (compacted, ops.SeqLayout in self._last_layout; position 0 of every sequence must be kept) and the outputs'
-        first layout.rows rows are the kept positions in order; attention_mask is not consulted."""
+        first layout.rows rows are the kept positions in order; attention_mask is not consulted.
+        img_packed / img_rows: the region projection's bf16 operand [B * img_rows, kpad] ready-made
+        (RegionStore.pretrain_batch(packed=True)) instead of img_feats and img_location_embeddings."""
         ops._require_hip(input_ids)
         dev = input_ids.device
         B, T = input_ids.shape
@@ -1056,6 +1059,13 @@ class BertImgModelwithLocationEmbeds(BertPreTrainedModel):
         else:
             encoder_history_states = None
         R = 0 if img_feats is None else img_feats.shape[1]
+        if img_packed is not None:
+            if _is_fp32(self):
+                raise NotImplementedError("the fp32 route does not take img_packed (a bf16 operand): build the batch with "
+                                          "RegionStore(..., dtype=torch.float32).pretrain_batch(..., packed=False)")
+            assert not encoder_history_states, "Cannot take image features while using encoder history states"
+            R = ops.packed_region_rows(img_packed, img_rows, img_feats, B, self._packed_img()[2], dev)
+        has_img = img_feats is not None or (img_packed is not None and R > 0)
         S = T + R
         H = self.config.hidden_size
 
@@ -1108,10 +1118,10 @@ class BertImgModelwithLocationEmbeds(BertPreTrainedModel):
                                     _f32(emb.LayerNorm.weight), _f32(emb.LayerNorm.bias), emb.LayerNorm.variance_epsilon, x32, S,
                                     err_flag=err)
             emb._last_err = err
-            if img_feats is not None:
+            if has_img:
                 _no_train_dropout(self, self.dropout.p)
                 w, b, kpad = self._packed_img()
-                a = ops.pack_concat(
+                a = img_packed if img_packed is not None else ops.pack_concat(
                     img_feats.reshape(B * R, -1).float().contiguous(),
                     img_location_embeddings.reshape(B * R, -1).float().contiguous(), kpad)
                 ops.linear(a, w, b, out=x32[T:], ldc=H, grp_rows=R, grp_stride=S, out_f32=True)
@@ -1132,10 +1142,10 @@ class BertImgModelwithLocationEmbeds(BertPreTrainedModel):
             return [out16], pooled, x32, B, S
         x = torch.empty((B * S, H), dtype=BF16, device=dev)
         self.embeddings.write_rows(x, S, input_ids, token_type_ids, position_ids)  # rows b*S + [0,T)
-        if img_feats is not None:
+        if has_img:
             _no_train_dropout(self, self.dropout.p)
             w, b, kpad = self._packed_img()
-            a = ops.pack_concat(
+            a = img_packed if img_packed is not None else ops.pack_concat(
                 img_feats.reshape(B * R, -1).float().contiguous(),
                 img_location_embeddings.reshape(B * R, -1).float().contiguous(), kpad)
             # rows b*S + T + r : the GEMM epilogue remaps its row m = b*R + r (replaces torch.cat, :287)
@@ -1193,9 +1203,11 @@ class BertImgModelwithLocationEmbeds(BertPreTrainedModel):
         return outs, pooled, x, B, S
 
     def forward(self, input_ids, token_type_ids=None, attention_mask=None, position_ids=None, head_mask=None,
-                img_feats=None, img_location_embeddings=None, encoder_history_states=None):
+                img_feats=None, img_location_embeddings=None, encoder_history_states=None, img_packed=None, img_rows=None):
         _refuse_data_parallel_replica(self)
         _poll_index_flags()   # an earlier call's out-of-range flag that has arrived since
+        if img_packed is not None and img_feats is not None:
+            raise ValueError("a batch carries img_feats or img_packed, not both")
         if self.training and not _is_fp32(self) and (
                 (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))
                 or self.config.hidden_dropout_prob > 0.0 or self.config.attention_probs_dropout_prob > 0.0):
@@ -1211,6 +1223,8 @@ class BertImgModelwithLocationEmbeds(BertPreTrainedModel):
                 raise NotImplementedError
             if img_feats is not None:
                 batch.update(img_feats=img_feats, img_location_embeddings=img_location_embeddings)
+            if img_packed is not None:
+                batch.update(img_packed=img_packed, img_rows=img_rows)
             dt = next(self.parameters()).dtype
             kw = dict(history=encoder_history_states) if encoder_history_states else {}   # (:271-274: text only, checked there)
             out = autograd_trunk_forward(self, batch, head_mask, want_hidden=self.encoder.output_hidden_states,
@@ -1220,7 +1234,8 @@ class BertImgModelwithLocationEmbeds(BertPreTrainedModel):
                 res = res + (tuple(h.to(dt) for h in extra),)
             return res
         outs, pooled, x, B, S = self.run_trunk(input_ids, token_type_ids, attention_mask, position_ids, head_mask,
-                                               img_feats, img_location_embeddings, encoder_history_states)
+                                               img_feats, img_location_embeddings, encoder_history_states,
+                                               img_packed=img_packed, img_rows=img_rows)
         dt = next(self.parameters()).dtype
         H = self.config.hidden_size
         f32 = None if _is_fp32(self) else self.encoder._final_f32
@@ -1238,6 +1253,8 @@ class BertImgModelwithLocationEmbeds(BertPreTrainedModel):
                          position_ids=position_ids)
             if img_feats is not None:
                 batch.update(img_feats=img_feats, img_location_embeddings=img_location_embeddings)
+            if img_packed is not None:
+                batch.update(img_packed=img_packed, img_rows=img_rows)
             sequence_output, pooled = lazy_autograd_trunk(self, batch, head_mask, sequence_output, pooled)
         outputs = (sequence_output, pooled)
         if self.encoder.output_hidden_states:
@@ -1362,15 +1379,18 @@ class PreTrainOscar(BertPreTrainedModel):
 
     def forward(self, input_ids, token_type_ids=None, attention_mask=None, labels=None, token_labels=None,
                 position_ids=None, head_mask=None, img_feats=None, img_location_embeddings=None, next_action=None,
-                text_only=False):
+                text_only=False, img_packed=None, img_rows=None):
         _refuse_data_parallel_replica(self)
+        if img_packed is not None and img_feats is not None:
+            raise ValueError("a batch carries img_feats or img_packed, not both")
         if text_only:
             return self.bert(input_ids, position_ids=position_ids, token_type_ids=token_type_ids,
                              attention_mask=attention_mask, head_mask=head_mask, img_feats=img_feats,
-                             img_location_embeddings=img_location_embeddings)
+                             img_location_embeddings=img_location_embeddings, img_packed=img_packed, img_rows=img_rows)
         batch = dict(input_ids=input_ids, token_type_ids=token_type_ids, attention_mask=attention_mask, labels=labels,
                      token_labels=token_labels, position_ids=position_ids, img_feats=img_feats,
-                     img_location_embeddings=img_location_embeddings, next_action=next_action)
+                     img_location_embeddings=img_location_embeddings, next_action=next_action, img_packed=img_packed,
+                     img_rows=img_rows if img_packed is not None else None)
         batch = {k: v for k, v in batch.items() if v is not None}
         wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         if wants_grad and _is_fp32(self):
@@ -1393,7 +1413,8 @@ class PreTrainOscar(BertPreTrainedModel):
 
             return _bridge_engine(self).forward_backward(batch, head_mask=head_mask, backward=False)
         outs, pooled, _, B, S = self.bert.run_trunk(
-            input_ids, token_type_ids, attention_mask, position_ids, head_mask, img_feats, img_location_embeddings)
+            input_ids, token_type_ids, attention_mask, position_ids, head_mask, img_feats, img_location_embeddings,
+            img_packed=img_packed, img_rows=img_rows)
         if token_labels is None:
             raise NameError("token_prediction")  # the reference leaves it unbound (encoder.py:400)
         if _is_fp32(self):

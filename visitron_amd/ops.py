@@ -1882,6 +1882,74 @@ def obs_gather_view(store, rows, B, out=None, err_flag=None):
     return out
 
 
+# ---- pretraining's region rows from a device region store (csrc/regions.hip) ---------------------------------------------------
+def region_gather(store, counts, loc_table, rows, D, text_labels, text_mask, text_token_classes, R, kpad=None, out=None,
+                  err_flag=None):
+    """One launch for a pretraining batch's region tensors.  store [N, 36, P, round_up(D, 8)] fp32 or bf16, counts uint8
+    [N, 36], loc_table fp32 [36, 36, 128], rows int32 [B, 2] = slot, current view, the text tensors int64 [B, T] (token
+    classes may be None), all on the device.  kpad None -> (img_feats fp32 [B, R, D], img_location_embeddings fp32 [B, R, 128],
+    labels, attention_mask, token_labels int64 [B, T + R]); kpad given -> (img_packed bf16 [B * R, kpad], labels,
+    attention_mask, token_labels).  out: the tensors to write into (contiguous), else they are allocated."""
+    _require_hip(store, counts, loc_table, rows, text_labels, text_mask, text_token_classes, err_flag)
+    assert store.dtype in (torch.float32, BF16) and store.dim() == 4 and store.is_contiguous()
+    N, V, P, ld = store.shape
+    assert ld == round_up(D, 8) and counts.dtype == torch.uint8 and tuple(counts.shape) == (N, V) and counts.is_contiguous()
+    assert loc_table.dtype == torch.float32 and tuple(loc_table.shape) == (36, 36, 128) and loc_table.is_contiguous()
+    assert rows.dtype == torch.int32 and rows.dim() == 2 and rows.shape[1] == 2 and rows.is_contiguous()
+    B, T = text_labels.shape
+    assert rows.shape[0] == B
+    for t in (text_labels, text_mask, text_token_classes):
+        assert t is None or (t.dtype == torch.int64 and tuple(t.shape) == (B, T) and t.is_contiguous())
+    dev = store.device
+    tok = text_token_classes is not None
+    packed = kpad is not None
+    shapes = (((B * R, kpad), BF16),) if packed else (((B, R, D), torch.float32), ((B, R, 128), torch.float32))
+    shapes += (((B, T + R), torch.int64),) * 3
+    if out is None:
+        out = tuple(torch.empty(s, dtype=dt, device=dev) for s, dt in shapes)
+        if not tok:
+            out = out[:-1] + (None,)
+    assert len(out) == len(shapes) and (out[-1] is not None) == tok
+    for t, (s, dt) in zip(out, shapes):
+        if t is not None:
+            _require_hip(t)
+            assert t.dtype == dt and tuple(t.shape) == s and t.is_contiguous()
+    if err_flag is not None:
+        assert err_flag.dtype == torch.int32 and err_flag.numel() == 1
+    head = (_ptr(store), int(store.dtype == BF16), N, V, P, D, _ptr(counts), _ptr(loc_table), _ptr(rows), _ptr(text_labels),
+            _ptr(text_mask), _ptr(text_token_classes), B, T, R)
+    tail = (_ptr(out[-3]), _ptr(out[-2]), _ptr(out[-1]), _ptr(err_flag), _stream())
+    if packed:
+        with _timed("region_gather_pack", 0.0, B * R * (float(store.element_size()) * D + 2.0 * kpad)):
+            rc = _lib.load().vt_region_gather_pack_bf16(*(head + (_ptr(out[0]), kpad) + tail))
+        _lib.check(rc, "vt_region_gather_pack_bf16")
+    else:
+        with _timed("region_gather", 0.0, B * R * (float(store.element_size()) * D + 4.0 * (D + 128))):
+            rc = _lib.load().vt_region_gather_f32(*(head + (_ptr(out[0]), _ptr(out[1])) + tail))
+        _lib.check(rc, "vt_region_gather_f32")
+    return out
+
+
+def packed_region_rows(img_packed, img_rows, img_feats, B, kpad, device):
+    """The checks on a batch that carries the region projection's operand ready-made (RegionStore.pretrain_batch(packed=True))
+    -> R.  img_packed must be contiguous bf16 [B * img_rows, kpad] on `device`, and img_feats must not come with it."""
+    if img_feats is not None:
+        raise ValueError("a batch carries img_feats or img_packed, not both")
+    if img_rows is None:
+        raise ValueError("img_packed needs img_rows, the region positions per sequence")
+    R = int(img_rows)
+    if not isinstance(img_packed, torch.Tensor) or img_packed.dtype != BF16:
+        raise ValueError("img_packed must be a bfloat16 tensor")
+    if R < 0 or tuple(img_packed.shape) != (B * R, kpad):
+        raise ValueError("img_packed must be [batch * img_rows, %d] = [%d, %d], got %s"
+                         % (kpad, B * R, kpad, tuple(img_packed.shape)))
+    if not img_packed.is_contiguous():
+        raise ValueError("img_packed must be contiguous")
+    if img_packed.device != torch.device(device):
+        raise ValueError("img_packed is on %s, the model on %s" % (img_packed.device, torch.device(device)))
+    return R
+
+
 # ---- fp32 parity path (csrc/fp32_path.hip): every operand, activation and accumulation in fp32 -----------------------
 def _f32ok(*ts):
     for t in ts:

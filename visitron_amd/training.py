@@ -610,6 +610,10 @@ class PretrainEngine(object):
         B, T = ids.shape
         img = batch.get("img_feats")
         R = 0 if img is None else img.shape[1]
+        packed = batch.get("img_packed")
+        if packed is not None:   # the region projection's operand as RegionStore.pretrain_batch(packed=True) wrote it
+            R = ops.packed_region_rows(packed, batch.get("img_rows"), img, B, self.kpad, dev)
+            img = packed if R > 0 else None   # (read only as "this batch has regions")
         S, H, I, nh, L = T + R, cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.num_hidden_layers
         M = B * S
         hist = None
@@ -730,8 +734,9 @@ class PretrainEngine(object):
         x0 = bufs.x0
         a_img = img_pre = None
         if img is not None:
-            a_img = ops.pack_concat(img.reshape(B * R, -1).float().contiguous(),
-                                    batch["img_location_embeddings"].reshape(B * R, -1).float().contiguous(), self.kpad)
+            a_img = packed if packed is not None else ops.pack_concat(
+                img.reshape(B * R, -1).float().contiguous(),
+                batch["img_location_embeddings"].reshape(B * R, -1).float().contiguous(), self.kpad)
             if getattr(m.bert, "use_img_layernorm", None):
                 # encoder.py:280-284: LayerNorm on the summed image embedding, THEN dropout; the pre-LayerNorm rows are
                 # kept (compact [B*R, H]) for the backward pass

@@ -70,6 +70,9 @@ def trunk_forward(eng, batch, head_mask, is_training):
     ids = _i64(batch["input_ids"])
     dev = ids.device
     B, T = ids.shape
+    if batch.get("img_packed") is not None:
+        raise NotImplementedError("PretrainEngine(precision='fp32') does not take img_packed (a bf16 operand): build the batch "
+                                  "with RegionStore(..., dtype=torch.float32).pretrain_batch(..., packed=False)")
     img = batch.get("img_feats")
     R = 0 if img is None else img.shape[1]
     S, H, nh, L = T + R, cfg.hidden_size, cfg.num_attention_heads, cfg.num_hidden_layers
