@@ -995,6 +995,25 @@ int vt_encoder_backward_seq_bf16(const vt_layer_weights* layers, const vt_layer_
 /* (p_hidden, p_attn, drop_seed: the values the forward used; layer0 = index of layers[0] in the full
  * stack when the backward is run over a sub-range of layers.) */
 
+/* ---- partly frozen stacks (ABI 22) ------------------------------------------------------------------------------
+ * In EVERY vt_encoder_backward_* entry point a layer whose vt_layer_grads holds twelve NULL pointers is frozen: no
+ * weight-gradient launch, its two LayerNorm backwards run without parameter gradients (and without the reduce launch and
+ * the weight prefetch riding in it), the dgrad chain and the attention backward run as usual.  Some but not all pointers
+ * NULL: VT_ERR_NULL.  With the side stream a frozen layer records no event; the waits follow what the call recorded.
+ * vt_layernorm_bwd_bf16 / _h_bf16 likewise take dgamma == dbeta == NULL as "dx only" (partial_ws is then not touched and
+ * may be NULL; dx and dx_dropped are bit for bit what the full call writes).
+ * This entry point is the three above in one (rows == 0: the padded layout with `mask`; rows > 0: compacted rows, mask
+ * must be NULL; ws_b / side_stream may be NULL) plus need_input_grad: 0 = nobody reads dL/d(x), so layers[0] does not
+ * launch its last dgrad GEMM (through the packed q|k|v projection; a frozen layers[0] launches nothing at all) and g is
+ * left undefined; != 0: as the others. */
+int vt_encoder_backward_partial_bf16(const vt_layer_weights* layers, const vt_layer_weights_t* layers_t,
+                                     const vt_layer_acts* acts, const vt_layer_grads* grads, int num_layers, const void* x,
+                                     const float* mask, int mask_additive, void* g, const vt_bwd_workspace* ws,
+                                     const vt_bwd_workspace* ws_b, int B, int S, int H, int nh, int I, float ln_eps,
+                                     int accumulate, float p_hidden, float p_attn, uint64_t drop_seed, int layer0,
+                                     int64_t rows, const int32_t* seq_start, const int32_t* seq_len, int need_input_grad,
+                                     vt_stream_t stream, vt_stream_t side_stream);
+
 #ifdef __cplusplus
 }
 #endif

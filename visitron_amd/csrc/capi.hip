@@ -21,7 +21,7 @@ const char* vt_error_string(int code) {
   }
 }
 
-int vt_abi_version(void) { return 21; }
+int vt_abi_version(void) { return 22; }
 
 // deterministic training mode (common.hpp): one word for the process, read by every dispatch at launch time
 void vt_set_deterministic(int on) { vt_deterministic_word().store(on ? 1 : 0, std::memory_order_relaxed); }
@@ -817,6 +817,19 @@ int vt_encoder_backward_seq_bf16(const vt_layer_weights* layers, const vt_layer_
   return vt_encoder_backward_dispatch(layers, layers_t, acts, grads, num_layers, x, nullptr, 0, g, ws, ws_b, B, S, H, nh, I,
                                       ln_eps, accumulate, p_hidden, p_attn, drop_seed, layer0, (hipStream_t)stream,
                                       (hipStream_t)side_stream, (long)rows, seq_start, seq_len);
+}
+
+int vt_encoder_backward_partial_bf16(const vt_layer_weights* layers, const vt_layer_weights_t* layers_t,
+                                     const vt_layer_acts* acts, const vt_layer_grads* grads, int num_layers, const void* x,
+                                     const float* mask, int mask_additive, void* g, const vt_bwd_workspace* ws,
+                                     const vt_bwd_workspace* ws_b, int B, int S, int H, int nh, int I, float ln_eps,
+                                     int accumulate, float p_hidden, float p_attn, uint64_t drop_seed, int layer0,
+                                     int64_t rows, const int32_t* seq_start, const int32_t* seq_len, int need_input_grad,
+                                     vt_stream_t stream, vt_stream_t side_stream) {
+  if (rows < 0) return VT_ERR_BAD_SHAPE;
+  return vt_encoder_backward_dispatch(layers, layers_t, acts, grads, num_layers, x, mask, mask_additive, g, ws, ws_b, B, S, H,
+                                      nh, I, ln_eps, accumulate, p_hidden, p_attn, drop_seed, layer0, (hipStream_t)stream,
+                                      (hipStream_t)side_stream, (long)rows, seq_start, seq_len, need_input_grad);
 }
 
 }  // the C ABI

@@ -73,7 +73,7 @@ int vt_encoder_backward_dispatch(const vt_layer_weights* layers, const vt_layer_
                                  int mask_additive, void* g, const vt_bwd_workspace* ws_a, const vt_bwd_workspace* ws_b, int B,
                                  int S, int H, int nh, int I, float ln_eps, int accumulate, float p_hidden, float p_attn,
                                  uint64_t drop_seed, int layer0, hipStream_t stream, hipStream_t side, long rows = 0,
-                                 const int* seq_start = nullptr, const int* seq_len = nullptr);
+                                 const int* seq_start = nullptr, const int* seq_len = nullptr, int need_input_grad = 1);
 int vt_weight_prefetch_set(int training_mode, int inference_mode);
 int vt_weight_prefetch_get(int inference);
 

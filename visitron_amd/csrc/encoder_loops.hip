@@ -195,13 +195,17 @@ static hipEvent_t* bwd_events(int which) {
 // kernel fills the rest.  Layer l works in workspace set (layer0 + l) & 1, so the buffers a wgrad still reads are
 // rewritten two layers later, behind a wait on that wgrad's completion event; before returning the main stream waits
 // for every wgrad of the call.
+// A layer whose vt_layer_grads holds twelve null pointers is FROZEN: it launches no weight gradient (and records no event:
+// the waits below look at what was recorded in this call only) and its two LayerNorm backwards run dx-only.
+// need_input_grad == 0: nobody reads dL/d(x) -- layers[0] skips its last dgrad GEMM (a frozen layers[0] is skipped
+// altogether) and g is left undefined.
 int vt_encoder_backward_dispatch(const vt_layer_weights* layers, const vt_layer_weights_t* layers_t,
                                  const vt_layer_acts* acts, const vt_layer_grads* grads, int num_layers, const void* x,
                                  const float* mask, int mask_additive, void* g, const vt_bwd_workspace* ws_a,
                                  const vt_bwd_workspace* ws_b, int B, int S, int H, int nh, int I, float ln_eps,
                                  int accumulate, float p_hidden, float p_attn, uint64_t drop_seed, int layer0,
                                  hipStream_t stream, hipStream_t side, long rows, const int* seq_start,
-                                 const int* seq_len) {
+                                 const int* seq_len, int need_input_grad) {
   if (!layers || !layers_t || !acts || !grads || !x || !g || !ws_a) return VT_ERR_NULL;
   if (rows && (!seq_start || !seq_len || mask || rows < 0 || rows > (long)B * S)) return VT_ERR_BAD_SHAPE;
   const bool overlap = ws_b != nullptr && side != nullptr && side != stream;
@@ -217,16 +221,27 @@ int vt_encoder_backward_dispatch(const vt_layer_weights* layers, const vt_layer_
   if (overlap && (!ev_in || !ev_done)) return VT_ERR_HIP;
   const int M = rows ? (int)rows : B * S;
   const bool prefetch = prefetch_training(M);
+  bool recorded[VT_BWD_MAX_LAYERS] = {};   // layers whose wgrad went to the side stream in THIS call
+  int last_recorded = -1;
   for (int l = num_layers - 1; l >= 0; --l) {
     const vt_layer_weights& w = layers[l];
     const vt_layer_weights_t& wt = layers_t[l];
     const vt_layer_acts& a = acts[l];
     const vt_layer_grads& d = grads[l];
+    float* const dptr[12] = {d.d_w_qkv, d.d_b_qkv, d.d_w_ao, d.d_b_ao, d.d_ln1_g, d.d_ln1_b,
+                             d.d_w_in, d.d_b_in, d.d_w_out, d.d_b_out, d.d_ln2_g, d.d_ln2_b};
+    int nset = 0;
+    for (int i = 0; i < 12; ++i) nset += dptr[i] != nullptr;
+    if (nset != 0 && nset != 12) return VT_ERR_NULL;   // a layer is trainable (all twelve) or frozen (none)
+    const bool frozen = nset == 0;
+    const bool input_grad = l > 0 || need_input_grad != 0;
+    if (frozen && !input_grad) continue;
     if (!a.mid_pre || !a.lse) return VT_ERR_NULL;
     const void* x_in = l == 0 ? x : acts[l - 1].out;
     const vt_bwd_workspace* ws = (overlap && ((layer0 + l) & 1)) ? ws_b : ws_a;
     // this layer rewrites the set that the wgrad of layer l + 2 reads
-    if (overlap && l + 2 < num_layers && hipStreamWaitEvent(stream, ev_done[l + 2], 0) != hipSuccess) return VT_ERR_HIP;
+    if (overlap && l + 2 < num_layers && recorded[l + 2] && hipStreamWaitEvent(stream, ev_done[l + 2], 0) != hipSuccess)
+      return VT_ERR_HIP;
     int rc;
     // dropout sites of this layer (the forward used layer index layer0 + l)
     if (!vt_attn_drop_ok(p_attn, vt_attn_drop_bits())) return VT_ERR_UNSUPPORTED;
@@ -264,8 +279,11 @@ int vt_encoder_backward_dispatch(const vt_layer_weights* layers, const vt_layer_
                                    rows ? seq_len : nullptr, rows, a.keep_bits);
     if (rc) return rc;
     // through the packed q|k|v projection, plus the residual branch: dL/d(layer input) -> g
-    rc = vt_gemm_dispatch(ws->g_qkv, 3L * H, wt.wt_qkv, 3L * H, nullptr, ws->g_pre2, H, g, H, M, H, 3 * H, VT_ACT_NONE, 0, 0, 0, stream);
-    if (rc) return rc;
+    if (input_grad) {
+      rc = vt_gemm_dispatch(ws->g_qkv, 3L * H, wt.wt_qkv, 3L * H, nullptr, ws->g_pre2, H, g, H, M, H, 3 * H, VT_ACT_NONE, 0, 0, 0, stream);
+      if (rc) return rc;
+    }
+    if (frozen) continue;
     // the four weight (+bias) gradients of this layer in one grouped launch
     WgradArgs wa;
     wa.nprob = 4;
@@ -285,13 +303,18 @@ int vt_encoder_backward_dispatch(const vt_layer_weights* layers, const vt_layer_
       rc = vt_wgrad_dispatch(wa, side);
       if (rc) return rc;
       if (hipEventRecord(ev_done[l], side) != hipSuccess) return VT_ERR_HIP;
+      recorded[l] = true;
+      last_recorded = l;
     } else {
       rc = vt_wgrad_dispatch(wa, stream);
       if (rc) return rc;
     }
   }
-  if (overlap)   // the caller's next work on the main stream (all-reduce, optimizer) sees every weight gradient
+  if (overlap) {   // the caller's next work on the main stream (all-reduce, optimizer) sees every weight gradient
     for (int l = (num_layers < 2 ? num_layers : 2) - 1; l >= 0; --l)
-      if (hipStreamWaitEvent(stream, ev_done[l], 0) != hipSuccess) return VT_ERR_HIP;
+      if (recorded[l] && hipStreamWaitEvent(stream, ev_done[l], 0) != hipSuccess) return VT_ERR_HIP;
+    // (the side stream runs in order: where layers 0 and 1 recorded nothing, the last event recorded covers the call)
+    if (last_recorded >= 2 && hipStreamWaitEvent(stream, ev_done[last_recorded], 0) != hipSuccess) return VT_ERR_HIP;
+  }
   return VT_OK;
 }

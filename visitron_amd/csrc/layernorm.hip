@@ -433,9 +433,12 @@ struct LnBwdArgs {
   float eps;
 };
 
-template <int CH, bool XF16>
+// PG = false is the dx-only form (a frozen LayerNorm: dgamma / dbeta are not wanted): no partial sums are kept, no partial row is
+// written and nothing is reduced afterwards; dx goes through the same instructions in the same order, so it is bit for bit the
+// full kernel's.
+template <int CH, bool XF16, bool PG = true>
 __global__ __launch_bounds__(256) void layernorm_bwd_rows(LnBwdArgs a) {
-  __shared__ float red[4][2][CH * 512];
+  __shared__ float red[PG ? 4 : 1][2][PG ? CH * 512 : 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float gam[CH][8], dg[CH][8], db[CH][8];
 #pragma unroll
@@ -489,8 +492,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows(LnBwdArgs a) {
         for (int i = 0; i < 8; ++i) {
           const float xh = (xv[c][i] - u) * rs;
           const float dyv = gv[c][i];
-          dg[c][i] += dyv * xh;
-          db[c][i] += dyv;
+          if (PG) {
+            dg[c][i] += dyv * xh;
+            db[c][i] += dyv;
+          }
           const float gg = dyv * gam[c][i];
           xv[c][i] = xh;
           gv[c][i] = gg;
@@ -521,6 +526,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows(LnBwdArgs a) {
       }
     }
   }
+  if (!PG) return;
   // block combine: 4 waves -> one partial row
 #pragma unroll
   for (int c = 0; c < CH; ++c)
@@ -547,10 +553,11 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows(LnBwdArgs a) {
 //    in flight where 8 TB/s needs ~ 64 KB;
 //  * the four reductions per row run on the vector ALU (wave_sum_valu) instead of 24 LDS-crossbar shuffles.
 // Same arithmetic per element as layernorm_bwd_rows; the in-lane summation order differs (last-bit differences in dx).
-template <int C8, int C4, int R, bool XF16>
+// (PG = false: the dx-only form, as in layernorm_bwd_rows.)
+template <int C8, int C4, int R, bool XF16, bool PG = true>
 __global__ __launch_bounds__(256) void layernorm_bwd_rows_full(LnBwdArgs a) {
   constexpr int E = 8 * C8 + 4 * C4, H = 512 * C8 + 256 * C4, W = E / 2;
-  __shared__ float red[4][2][H];
+  __shared__ float red[PG ? 4 : 1][2][PG ? H : 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int col4 = 512 * C8 + lane * 4;
   float gam[E], dg[E], db[E];
@@ -633,8 +640,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows_full(LnBwdArgs a) {
       for (int e = 0; e < E; ++e) {
         const float xh = (xv[r][e] - u[r]) * rs[r];
         const float dyv = gv[r][e];
-        dg[e] += dyv * xh;
-        db[e] += dyv;
+        if (PG) {
+          dg[e] += dyv * xh;
+          db[e] += dyv;
+        }
         const float gg = dyv * gam[e];
         xv[r][e] = xh;
         gv[r][e] = gg;
@@ -682,6 +691,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows_full(LnBwdArgs a) {
       }
     }
   }
+  if (!PG) return;
   // block combine: 4 waves -> one partial row
 #pragma unroll
   for (int e = 0; e < E; ++e) {
@@ -744,7 +754,10 @@ int vt_layernorm_bwd_dispatch(const void* x, long ldx, const void* dy, long ldy,
                               float* dgamma, float* dbeta, float* partial_ws, int M, int H, float eps, int accumulate,
                               hipStream_t stream, void* dx2, long lddx2, const DropCfg* drop, int x_f16,
                               const PrefetchArgs* pf) {
-  if (!x || !dy || !gamma || !dx || !dgamma || !dbeta || !partial_ws) return VT_ERR_NULL;
+  // dgamma == dbeta == NULL: dx only (the LayerNorm's parameters are frozen) -- the kernels' PG = false forms, no reduce launch,
+  // partial_ws not touched (may be NULL) and the weight prefetch that rides in the reduce launch dropped with it
+  const bool pg = dgamma != nullptr || dbeta != nullptr;
+  if (!x || !dy || !gamma || !dx || (pg && (!dgamma || !dbeta || !partial_ws))) return VT_ERR_NULL;
   if (M <= 0 || H <= 0 || (H % 8) || H > 1024) return VT_ERR_BAD_SHAPE;
   if ((ldx % 8) || (ldy % 8) || (lddx % 8) || (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15)) return VT_ERR_BAD_ALIGN;
   LnBwdArgs a;
@@ -763,10 +776,14 @@ int vt_layernorm_bwd_dispatch(const void* x, long ldx, const void* dy, long ldy,
     const int R = rows_per_wave >= 4 ? 4 : rows_per_wave >= 2 ? 2 : 1;
     nblocks = (int)((((long)M + R - 1) / R + 3) / 4);
     if (nblocks > LN_BWD_MAX_BLOCKS) nblocks = LN_BWD_MAX_BLOCKS;
+#define VT_LNB_LAUNCH_PG(C8, C4, RR, PG)                                                                                   \
+    do {                                                                                                                   \
+      if (x_f16) hipLaunchKernelGGL((layernorm_bwd_rows_full<C8, C4, RR, true, PG>), dim3(nblocks), dim3(256), 0, stream, a); \
+      else hipLaunchKernelGGL((layernorm_bwd_rows_full<C8, C4, RR, false, PG>), dim3(nblocks), dim3(256), 0, stream, a);   \
+    } while (0)
 #define VT_LNB_LAUNCH(C8, C4, RR)                                                                                        \
     do {                                                                                                                 \
-      if (x_f16) hipLaunchKernelGGL((layernorm_bwd_rows_full<C8, C4, RR, true>), dim3(nblocks), dim3(256), 0, stream, a);  \
-      else hipLaunchKernelGGL((layernorm_bwd_rows_full<C8, C4, RR, false>), dim3(nblocks), dim3(256), 0, stream, a);      \
+      if (pg) VT_LNB_LAUNCH_PG(C8, C4, RR, true); else VT_LNB_LAUNCH_PG(C8, C4, RR, false);                              \
     } while (0)
 #define VT_LNB_SHAPE(RR)                                                                                                 \
     do {                                                                                                                 \
@@ -776,14 +793,18 @@ int vt_layernorm_bwd_dispatch(const void* x, long ldx, const void* dy, long ldy,
     if (R == 4) VT_LNB_SHAPE(4); else if (R == 2) VT_LNB_SHAPE(2); else VT_LNB_SHAPE(1);
 #undef VT_LNB_SHAPE
 #undef VT_LNB_LAUNCH
-  } else if (H <= 512) {
-    if (x_f16) hipLaunchKernelGGL((layernorm_bwd_rows<1, true>), dim3(nblocks), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((layernorm_bwd_rows<1, false>), dim3(nblocks), dim3(256), 0, stream, a);
+#undef VT_LNB_LAUNCH_PG
   } else {
-    if (x_f16) hipLaunchKernelGGL((layernorm_bwd_rows<2, true>), dim3(nblocks), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((layernorm_bwd_rows<2, false>), dim3(nblocks), dim3(256), 0, stream, a);
+#define VT_LNB_CHUNKED(CH, PG)                                                                                           \
+    do {                                                                                                                 \
+      if (x_f16) hipLaunchKernelGGL((layernorm_bwd_rows<CH, true, PG>), dim3(nblocks), dim3(256), 0, stream, a);         \
+      else hipLaunchKernelGGL((layernorm_bwd_rows<CH, false, PG>), dim3(nblocks), dim3(256), 0, stream, a);              \
+    } while (0)
+    if (H <= 512) { if (pg) VT_LNB_CHUNKED(1, true); else VT_LNB_CHUNKED(1, false); }
+    else { if (pg) VT_LNB_CHUNKED(2, true); else VT_LNB_CHUNKED(2, false); }
+#undef VT_LNB_CHUNKED
   }
-  {
+  if (pg) {
     const int n_main = (2 * H + 15) / 16;
     PrefetchArgs none;
     none.n = 0;

@@ -850,17 +850,21 @@ def attention_bwd(qkv, dctx, ctx, lse, B, S, nh, mask=None, mask_additive=False,
 def layernorm_bwd(x, dy, gamma, eps, dgamma, dbeta, dx=None, ws=None, accumulate=False, M=None, dx_dropped=None,
                   drop=NO_DROP):
     """dx (bf16) and dgamma/dbeta (fp32, in place) of BertLayerNorm; x = pre-LayerNorm input.
-    dx_dropped (optional bf16 [M,H]) receives dx * dropout mask / (1-p) of site `drop`."""
+    dx_dropped (optional bf16 [M,H]) receives dx * dropout mask / (1-p) of site `drop`.
+    dgamma = dbeta = None (a frozen LayerNorm): dx only -- the same dx bit for bit, no partial sums, no reduce launch, ws not
+    touched (profiled as "layernorm_bwd_dx")."""
     _require_hip(x, dy, gamma, dgamma, dbeta, dx)
+    if (dgamma is None) != (dbeta is None):
+        raise ValueError("layernorm_bwd takes dgamma and dbeta together, or neither")
     H = gamma.numel()
     if M is None:
         M = x.shape[0]
     if dx is None:
         dx = torch.empty((M, H), dtype=BF16, device=x.device)
-    if ws is None:
+    if ws is None and dgamma is not None:
         ws = torch.empty(LN_BWD_WS_ROWS * 2 * H, dtype=torch.float32, device=x.device)
     fn = "vt_layernorm_bwd_h_bf16" if x.dtype == F16 else "vt_layernorm_bwd_bf16"   # x: the pre-LayerNorm sums, bf16 or fp16
-    with _timed("layernorm_bwd_rows", 0.0, 6.0 * M * H):
+    with _timed("layernorm_bwd_rows" if dgamma is not None else "layernorm_bwd_dx", 0.0, 6.0 * M * H):
         rc = getattr(_lib.load(), fn)(
             _ptr(x), x.stride(0), _ptr(dy), dy.stride(0), _ptr(gamma), _ptr(dx), dx.stride(0), _ptr(dgamma),
             _ptr(dbeta), _ptr(ws), M, H, float(eps), 1 if accumulate else 0, _ptr(dx_dropped),
@@ -1316,10 +1320,22 @@ def dgelu_mul(g, h, out=None):
 
 def encoder_backward(layer_weights, layer_weights_t, layer_acts, layer_grads, x, mask, mask_additive, g, ws,
                      B, S, H, nh, I, eps, accumulate=False, p_hidden=0.0, p_attn=0.0, drop_seed=0, layer0=0,
-                     ws_b=None, side_stream=None, seq=None):
+                     ws_b=None, side_stream=None, seq=None, need_input_grad=True):
     """Reverse layer loop in C; g [B*S,H] bf16 is updated in place to dL/dx.  With a second workspace set and a side
-    stream (torch.cuda.Stream) the weight gradients of a layer run beside the next layer's dgrad chain."""
+    stream (torch.cuda.Stream) the weight gradients of a layer run beside the next layer's dgrad chain.
+    A layer_grads row of null pointers is a frozen layer (no weight gradient, LayerNorm backward dx-only).
+    need_input_grad=False: nobody reads dL/dx -- the first layer's last dgrad GEMM is not launched and g is left undefined."""
     _require_hip(x, mask, g)
+    if not need_input_grad:
+        assert seq is None or mask is None
+        rc = _lib.load().vt_encoder_backward_partial_bf16(
+            layer_weights, layer_weights_t, layer_acts, layer_grads, len(layer_weights), _ptr(x), _ptr(mask),
+            _mask_mode(mask, mask_additive, B, S), _ptr(g), ctypes.byref(ws), None if ws_b is None else ctypes.byref(ws_b),
+            B, S, H, nh, I, float(eps), 1 if accumulate else 0, float(p_hidden), float(p_attn), int(drop_seed), int(layer0),
+            0 if seq is None else seq.rows, None if seq is None else _ptr(seq.start), None if seq is None else _ptr(seq.length),
+            0, _stream(), None if side_stream is None else ctypes.c_void_p(side_stream.cuda_stream))
+        _lib.check(rc, "vt_encoder_backward_partial_bf16")
+        return
     if seq is not None:
         assert mask is None
         rc = _lib.load().vt_encoder_backward_seq_bf16(

@@ -69,10 +69,17 @@ class FlatParams(object):
         for n, p, o, cnt, _ in self.entries:
             self.p[o:o + cnt].copy_(p.data.reshape(-1))
             p.data = self.p[o:o + cnt].view(p.shape)
-            if attach_grads:
-                p.grad = self.g[o:o + cnt].view(p.shape)
             self.off[n] = (o, cnt, tuple(p.shape))
+        # an entry's span: its elements and the padding up to the next entry (the padding belongs to no parameter and holds zeros)
+        starts = [o for _, _, o, _, _ in self.entries] + [self.total]
+        self.span = {n: (o, nxt) for (n, _, o, _, _), nxt in zip(self.entries, starts[1:])}
+        self._params = [p for _, p, _, _, _ in self.entries]
+        self.reattach_grads()
         self.refresh_mirror()
+
+    def flags(self):
+        """requires_grad of every entry, in slab order (read at every step: PretrainEngine._sync_trainable)."""
+        return tuple([p.requires_grad for p in self._params])
 
     def owns_params(self):
         """False once something re-pointed a parameter's storage (another engine built over the same parameters -- the
@@ -100,11 +107,14 @@ class FlatParams(object):
         return slab[o:o + cnt].view(shp)
 
     def reattach_grads(self):
-        """optimizer.zero_grad(set_to_none=True) drops p.grad; point them back at the slab."""
+        """optimizer.zero_grad(set_to_none=True) drops p.grad; point them back at the slab.  A parameter that does not
+        require grad has no gradient: its p.grad is None (its range of the slab is scratch nobody exposes)."""
         if not self.attach_grads:
             return
         for n, p, o, cnt, _ in self.entries:
-            if p.grad is None or p.grad.data_ptr() != self.g.data_ptr() + 4 * o:
+            if not p.requires_grad:
+                p.grad = None
+            elif p.grad is None or p.grad.data_ptr() != self.g.data_ptr() + 4 * o:
                 p.grad = self.g[o:o + cnt].view(p.shape)
 
 
@@ -160,6 +170,86 @@ _HEAD_TABLE = (
     ("region", "bert.LayerNorm.weight", None), ("region", "bert.LayerNorm.bias", None),   # (with use_img_layernorm only)
 )
 _HEAD_GROUPS = ("mlm", "token", "action", "pooler")   # final before the encoder backward starts; "region" is not
+
+# ---- requires_grad: what a frozen parameter costs is decided per UNIT, the parameters one backward launch group feeds -- an
+# encoder layer (its 16 tensors), the embedding block (word / position / type tables and their LayerNorm; a tied MLM decoder IS
+# the word table), and _HEAD_TABLE's groups.  A unit with no trainable member is not computed; a mixed one is computed whole
+# and only its trainable members are exposed, reduced and stepped.
+SHARD_FROZEN_MSG = ("shard_optimizer=True serves a model whose parameters all require grad: the ownership plan cuts the whole "
+                    "slab, and a frozen parameter would be reduced, updated and gathered with it")
+SHARD_STEPS_MSG = ("shard_optimizer=True serves parameters that all took the same number of updates (one bias correction "
+                   "per launch); this state counts them differently (it comes from a run that unfroze parameters later)")
+
+
+def unit_flags(names, flags, num_layers, tied_decoder=True):
+    """Which units have a trainable member -> dict(layers=[bool] * L, emb=, region=, mlm=, token=, action=, pooler=).
+    names / flags: the slab entries' names and requires_grad.  tied_decoder: the MLM decoder weight is the word table
+    (it has no entry of its own), so a trainable word table keeps the "mlm" group computed -- its decoder launch feeds it."""
+    group_of = {path: grp for grp, path, _ in _HEAD_TABLE}
+    units = dict(layers=[False] * num_layers, emb=False, **{grp: False for grp in _HEAD_GROUPS + ("region",)})
+    for n, fl in zip(names, flags):
+        if not fl:
+            continue
+        if n.startswith("bert.encoder.layer."):
+            units["layers"][int(n.split(".")[3])] = True
+        elif n.startswith("bert.embeddings."):
+            units["emb"] = True
+            if tied_decoder and n == "bert.embeddings.word_embeddings.weight":
+                units["mlm"] = True
+        elif n in group_of:
+            units[group_of[n]] = True
+        else:
+            raise KeyError("parameter %s belongs to no unit" % n)
+    return units
+
+
+def backward_stop(layer_flags, below, history_need=None):
+    """Where the reverse layer loop may stop -> (lo, need_input_grad): it runs layers L-1 .. lo (none when lo == L), and
+    layer lo must produce dL/d(its input) only with need_input_grad.  below: something under the layers wants the gradient
+    (a trainable embedding block or region group, a caller's d_hidden); history_need[l]: the history tensor of layer l
+    requires grad (its gradient comes out of layer l's last dgrad, which that layer then runs for it)."""
+    if below:
+        return 0, True
+    for l, fl in enumerate(layer_flags):
+        if fl or (history_need is not None and history_need[l]):
+            return l, False
+    return len(layer_flags), False
+
+
+def merge_spans(spans):
+    """[start, end) spans sorted and merged where they touch or overlap."""
+    out = []
+    for s_, e_ in sorted(spans):
+        if out and s_ <= out[-1][1]:
+            out[-1] = (out[-1][0], max(out[-1][1], e_))
+        elif e_ > s_:
+            out.append((s_, e_))
+    return out
+
+
+def intersect_ranges(ranges, spans):
+    """The parts of `ranges` (in their order) inside the sorted disjoint `spans`."""
+    out = []
+    for s_, e_ in ranges:
+        for a_, b_ in spans:
+            lo, hi = max(s_, a_), min(e_, b_)
+            if hi > lo:
+                out.append((lo, hi))
+    return out
+
+
+def step_segments(entries, flags, steps):
+    """AdamW's launches over the trainable entries: maximal runs of adjacent spans whose parameters took the same number of
+    updates -> [(start, end, updates so far)].  entries: (name, (start, end)) in slab order."""
+    segs = []
+    for (n, (s_, e_)), fl in zip(entries, flags):
+        if not fl:
+            continue
+        if segs and segs[-1][1] == s_ and segs[-1][2] == steps[n]:
+            segs[-1] = (segs[-1][0], e_, steps[n])
+        else:
+            segs.append((s_, e_, steps[n]))
+    return segs
 
 
 class TrunkState(object):
@@ -406,6 +496,10 @@ class PretrainEngine(object):
         if precision == "fp32" and self.world > 1:
             raise NotImplementedError("PretrainEngine(precision='fp32') serves one rank")
         self.flat = FlatParams(model, attach_grads=attach_grads, moments=not self.shard)
+        # updates each parameter has taken (torch's per-parameter state["step"]: a parameter unfrozen later starts its bias
+        # correction at its own first update); the tables below follow requires_grad, read at every step (_sync_trainable)
+        self.param_steps = {n: 0 for n, _, _, _, _ in self.flat.entries}
+        self._flags = None
         self.bucket_elems = int(bucket_mb * 1024 * 1024 // 4)
         self.loss_scale_by_world = loss_scale_by_world
         # data-parallel gradient exchange: the reference's DDP moves 452 MB of fp32 buckets per step (pretrain.py:96-102);
@@ -432,6 +526,7 @@ class PretrainEngine(object):
         self.last_drop_seed = 0
         self._wt_dirty = True
         self._wt_batch = None
+        self._wt_batch_moved = None   # (flags, the batch over the matrices with a trainable source)
         # weight gradients on a side stream beside the next layer's dgrad chain: opt-in (VT_OVERLAP_WGRAD=1 or the
         # attribute).  Measured on one GPU: +1 % when the GEMMs are the one-tile-per-workgroup kernels, -1 % with the
         # persistent kernel (its workgroups queue behind the wgrad's and still do a full share each); with a second
@@ -458,11 +553,47 @@ class PretrainEngine(object):
             training_f32.setup(self)
         else:
             self._build_tables()
+        self._sync_trainable()
         self.plan = None
         if self.shard:
             self._shard_setup()
 
     # ------------------------------------------------------------------------------ tables
+    def _sync_trainable(self):
+        """requires_grad is read at every step: when the tuple of flags changed (or on the first call) the tables that depend
+        on it are rebuilt -- the unit flags, the layer gradient table of the C loop (a frozen layer: null pointers), the
+        trainable spans of the slab (what is all-reduced) and AdamW's segments (what is stepped, with which update count)."""
+        f = self.flat
+        flags = f.flags()
+        if self.shard_optimizer and not all(flags):
+            raise NotImplementedError(SHARD_FROZEN_MSG)
+        if flags == self._flags:
+            return
+        self._flags = flags
+        names = [n for n, _, _, _, _ in f.entries]
+        self._trainable = dict(zip(names, flags))
+        self.units = unit_flags(names, flags, self.cfg.num_hidden_layers, self.has_heads and self._decoder_tied())
+        self.train_spans = merge_spans([f.span[n] for n in names if self._trainable[n]])
+        self._rebuild_segments()
+        f.reattach_grads()   # a parameter frozen since the last step loses its .grad, an unfrozen one gets its slab view
+        if self.precision == "bf16":
+            for i, lv in enumerate(self._layers):
+                for k, v in lv.gr.items():
+                    setattr(self.g_tab[i], "d_" + k, v.data_ptr() if self.units["layers"][i] else None)
+
+    def _rebuild_segments(self):
+        f = self.flat
+        self.adam_segments = step_segments([(n, f.span[n]) for n, _, _, _, _ in f.entries], self._flags, self.param_steps)
+        if self.shard_optimizer and len(set(self.param_steps.values())) > 1:
+            raise NotImplementedError(SHARD_STEPS_MSG)
+
+    def _trainable_ranges(self, ranges):
+        """The trainable parts of slab ranges (a frozen parameter's range is neither all-reduced nor stepped)."""
+        return intersect_ranges(ranges, self.train_spans)
+
+    def _is_trainable(self, param):
+        return self._trainable[self._name_of(param)]
+
     def _build_tables(self):
         self._wt_batch = None
         m, f, cfg = self.model, self.flat, self.cfg
@@ -540,7 +671,10 @@ class PretrainEngine(object):
         return self.flat.view(self.flat.g, self._name_of(param))
 
     def refresh_derived_weights(self):
-        """Transposed / packed bf16 copies that the dgrad GEMMs and the region projection read."""
+        """Transposed / packed bf16 copies that the dgrad GEMMs and the region projection read.  _wt_dirty: True = all of them
+        (a new engine, parameters written from outside the step); a tuple of flags = the engine's own AdamW ran under those
+        requires_grad flags, so only the copies of matrices with a source that was trainable THEN changed -- a frozen
+        matrix's copy is not rebuilt."""
         if self.flat.mirror_is_stale():
             self.flat.refresh_mirror()
             self._wt_dirty = True
@@ -548,14 +682,38 @@ class PretrainEngine(object):
             return
         m, D = self.model, self.model.bert.img_dim
         if self._wt_batch is None:   # all layers' four matrices + the head matrices: one launch
-            pairs = [(lv.t["w_" + k[3:]], dst) for lv in self._layers for k, dst in lv.wt.items()]
-            pairs += [(self._mirror(prm), self.head_t[key]) for _, prm, key in self._head_rows() if key]
-            self._wt_batch = ops.TransposeBatch(pairs)
-        self._wt_batch.run()
-        self.w_img[:, :D].copy_(self._mirror(m.bert.img_embedding.weight))
-        self.w_img[:, D:D + 128].copy_(self._mirror(m.bert.location_embeds.weight))
-        torch.add(m.bert.img_embedding.bias.detach(), m.bert.location_embeds.bias.detach(), out=self.b_img)
+            self._wt_batch = ops.TransposeBatch([(src, dst) for src, dst, _ in self._transpose_pairs(self._flags)])
+        stepped = self._wt_dirty
+        moved_only = stepped is not True and not all(stepped)
+        region_moved = True
+        if moved_only:
+            if self._wt_batch_moved is None or self._wt_batch_moved[0] != stepped:
+                pairs = [(src, dst) for src, dst, moved in self._transpose_pairs(stepped) if moved]
+                self._wt_batch_moved = (stepped, ops.TransposeBatch(pairs) if pairs else None)
+            if self._wt_batch_moved[1] is not None:
+                self._wt_batch_moved[1].run()
+            region_moved = any(fl for (n, _, _, _, _), fl in zip(self.flat.entries, stepped)
+                               if n.startswith(("bert.img_embedding.", "bert.location_embeds.")))
+        else:
+            self._wt_batch.run()
+        if region_moved:
+            self.w_img[:, :D].copy_(self._mirror(m.bert.img_embedding.weight))
+            self.w_img[:, D:D + 128].copy_(self._mirror(m.bert.location_embeds.weight))
+            torch.add(m.bert.img_embedding.bias.detach(), m.bert.location_embeds.bias.detach(), out=self.b_img)
         self._wt_dirty = False
+
+    def _transpose_pairs(self, flags):
+        """(source in the mirror, transposed copy, does a parameter trainable under `flags` lie in the source) for every
+        layer's four matrices and the head matrices, in the batch's order."""
+        out, trainable = [], dict(zip((n for n, _, _, _, _ in self.flat.entries), flags))
+        for l, lv in enumerate(self._layers):
+            pre = "bert.encoder.layer.%d." % l
+            for k, dst in lv.wt.items():
+                field = "w_" + k[3:]
+                names = [_LAYER_PACKED[field] % x for x in _QKV] if field in _LAYER_PACKED else [_LAYER_FIELDS[field]]
+                out.append((lv.t[field], dst, any(trainable[pre + n] for n in names)))
+        out += [(self._mirror(prm), self.head_t[key], trainable[self._name_of(prm)]) for _, prm, key in self._head_rows() if key]
+        return out
 
     def _buffers(self, B, S):
         key = (B, S)
@@ -779,7 +937,8 @@ class PretrainEngine(object):
         (1 - m) * -10000 arithmetic) or the reference's 3-D form [B, S, S] (encoder.py:228-229); head_mask as the
         reference takes it (encoder.py:248-265; the layer loop then runs op by op: the head scaling sits between the
         attention kernel and the output projection in both directions).  backward=False: the forward and its 7-tuple only."""
-        if self.precision == "fp32":
+        self._sync_trainable()
+        if self.precision == "fp32":   # (honours requires_grad in what it exposes and steps; computes every gradient)
             if comm is not None:
                 raise NotImplementedError("PretrainEngine(precision='fp32') serves one rank")
             return training_f32.forward_backward(self, batch, grad_scale, accumulate, head_mask, backward)
@@ -862,6 +1021,9 @@ class PretrainEngine(object):
         V, C, A = cfg.vocab_size, cfg.detector_classes, cfg.action_space
         mlm, tok, act = kept
         pr, lin_tok, emb = m.mlmhead.predictions, m.token_head[0], m.bert.embeddings
+        # frozen units: a head group without a trainable member launches no weight gradient, and where nothing in the trunk
+        # wants dL/d(sequence output) either (st-independent: _trunk_wants_grad) the head's dgrad is not launched
+        un, below = self.units, self._trunk_wants_grad(st)
         # dL/d(sequence output): zero except at the supervised / [CLS] rows.  Assembled directly in the bf16 buffer the
         # encoder backward reads (a row normally belongs to one head; where two heads meet the sum is formed in bf16)
         g16 = bufs.g[:st.Mr]
@@ -873,11 +1035,25 @@ class PretrainEngine(object):
         # defined values before that: with a tied decoder and supervised rows the decoder's weight gradient -- the first
         # thing written into it -- simply overwrites all of it (no 94 MB fill, no read-back by an accumulating launch)
         dec_overwrites = dec_w_is_tied and Ml > 0 and pr.decoder.weight.shape[0] == emb.word_embeddings.weight.shape[0]
+        # (a frozen word table: its range of the slab is scratch that nothing exposes, reduces or steps -- the 94 MB fill is
+        # dropped; a mixed "mlm" group or embedding block still writes into it, as units are computed whole)
         if not acc and not dec_overwrites:
-            word_grad.zero_()
-            if dec_w_is_tied:
+            if self._is_trainable(emb.word_embeddings.weight):
+                word_grad.zero_()
+            if dec_w_is_tied and un["mlm"]:
                 self._grad(pr.bias).zero_()  # shares the accumulate flag of the tied decoder weight below
-        if mlm is not None:
+        if mlm is not None and not (un["mlm"] or below):
+            pass   # frozen head over a trunk that wants nothing from it
+        elif mlm is not None and not un["mlm"]:
+            # frozen head, trainable trunk: the dgrad chain alone (the LayerNorm backward in its dx-only form)
+            dl, t1 = mlm["dl"], mlm["t1"]
+            ks = ops.splitk_for(Ml, H, self.Vp)
+            g_t2 = ops.linear_splitk(dl, self.head_t["dec"], ks) if ks else ops.linear(dl, self.head_t["dec"])
+            g_t1 = ops.layernorm_bwd(t1, g_t2, pr.transform.LayerNorm.weight.detach(), pr.transform.LayerNorm.variance_epsilon,
+                                     None, None)
+            g_ht = ops.dgelu_mul(g_t1, mlm["h_t"])
+            g16.index_add_(0, st.rows_w, ops.linear(g_ht, self.head_t["tr"]))
+        elif mlm is not None:
             dl, t1, t2 = mlm["dl"], mlm["t1"], mlm["t2"]
             dec_grad = self._grad(pr.decoder.weight)
             ops.wgrad([dict(dy=dl[:, :V], x=t2, dw=dec_grad, db=self._grad(pr.bias),
@@ -890,25 +1066,32 @@ class PretrainEngine(object):
                                      ws=bufs.ws_t["ln_partial"], accumulate=acc)
             g_ht = ops.dgelu_mul(g_t1, mlm["h_t"])
             ops.wgrad([wg(g_ht, mlm["x"], self._grad(pr.transform.dense.weight), self._grad(pr.transform.dense.bias))], Ml)
-            g16.index_add_(0, st.rows_w, ops.linear(g_ht, self.head_t["tr"]))
+            if below:
+                g16.index_add_(0, st.rows_w, ops.linear(g_ht, self.head_t["tr"]))
         elif not acc:
             # no supervised MLM row (the loss is NaN, as the reference's): the head's gradients must not keep the
             # previous step's values (a tied decoder's weight -- the word table -- was zeroed above)
             self._zero_head_grads("mlm")
         if tok is not None:
-            ops.wgrad([wg(tok["dl"][:, :C], tok["x"], self._grad(lin_tok.weight), self._grad(lin_tok.bias))], Mt)
-            g16.index_add_(0, st.rows_t, ops.linear(tok["dl"], self.head_t["tok"]))
+            if un["token"]:
+                ops.wgrad([wg(tok["dl"][:, :C], tok["x"], self._grad(lin_tok.weight), self._grad(lin_tok.bias))], Mt)
+            if below:
+                g16.index_add_(0, st.rows_t, ops.linear(tok["dl"], self.head_t["tok"]))
         elif not acc:
             self._zero_head_grads("token")
         if act is not None:
             dla_bf, pooled = act["dl"], st.pooled
-            ops.wgrad([wg(dla_bf[:, :A], st.pooled_bf, self._grad(m.next_action.linear.weight),
-                          self._grad(m.next_action.linear.bias))], B)
-            g_pooled = ops.linear(dla_bf, self.head_t["act"], out_f32=True)
-            g_z = (g_pooled * (1.0 - pooled * pooled)).to(BF16)
-            ops.wgrad([wg(g_z, seq.view(B, S * H)[:, :H] if st.lay is None else st.cls_seq,
-                          self._grad(m.bert.pooler.dense.weight), self._grad(m.bert.pooler.dense.bias))], B)
-            g16.index_add_(0, st.cls_rows, ops.linear(g_z, self.head_t["pool"]))
+            if un["action"]:
+                ops.wgrad([wg(dla_bf[:, :A], st.pooled_bf, self._grad(m.next_action.linear.weight),
+                              self._grad(m.next_action.linear.bias))], B)
+            if un["pooler"] or below:
+                g_pooled = ops.linear(dla_bf, self.head_t["act"], out_f32=True)
+                g_z = (g_pooled * (1.0 - pooled * pooled)).to(BF16)
+            if un["pooler"]:
+                ops.wgrad([wg(g_z, seq.view(B, S * H)[:, :H] if st.lay is None else st.cls_seq,
+                              self._grad(m.bert.pooler.dense.weight), self._grad(m.bert.pooler.dense.bias))], B)
+            if below:
+                g16.index_add_(0, st.cls_rows, ops.linear(g_z, self.head_t["pool"]))
         elif not acc:
             self._zero_head_grads("action", "pooler")
 
@@ -917,30 +1100,42 @@ class PretrainEngine(object):
         return self._head_group(*_HEAD_GROUPS)
 
     def _param_ranges(self, params):
-        """Slab ranges [start, end) of the given parameters, ends rounded up to the alignment granule (the padding belongs
-        to no parameter), sorted and merged where they touch."""
+        """Slab ranges [start, end) of the trainable ones among the given parameters, ends rounded up to the alignment
+        granule (the padding belongs to no parameter), sorted and merged where they touch."""
         f, spans = self.flat, []
         for prm in params:
-            o, cnt, _ = f.off[self._name_of(prm)]
+            name = self._name_of(prm)
+            if not self._trainable[name]:
+                continue
+            o, cnt, _ = f.off[name]
             spans.append((o, min(round_up(o + cnt, ALIGN), f.total)))
-        out = []
-        for s_, e_ in sorted(spans):
-            if out and s_ <= out[-1][1]:
-                out[-1] = (out[-1][0], max(out[-1][1], e_))
-            else:
-                out.append((s_, e_))
-        return out
+        return merge_spans(spans)
 
     def _layer_chunk_ranges(self, lo, hi):
         """The decay and the no-decay slab range of layers [lo, hi), ends rounded up to the slab's alignment granule (the
-        padding belongs to no parameter)."""
-        return [(self.layer_ranges[lo][k][0], min(round_up(self.layer_ranges[hi - 1][k][1], ALIGN), self.flat.total))
-                for k in (0, 1)]
+        padding belongs to no parameter) -- their trainable parts."""
+        return self._trainable_ranges(
+            [(self.layer_ranges[lo][k][0], min(round_up(self.layer_ranges[hi - 1][k][1], ALIGN), self.flat.total))
+             for k in (0, 1)])
+
+    def _trunk_wants_grad(self, st, d_hidden=None):
+        """Does anything in the trunk read dL/d(sequence output)?  A trainable layer, embedding block or region group (the
+        latter with regions in the batch only), a caller's d_hidden, a history tensor that requires grad."""
+        un = self.units
+        return bool(any(un["layers"]) or un["emb"] or (un["region"] and st.img is not None) or d_hidden is not None
+                    or (st.hist is not None and any(st.hist["need"])))
+
+    def _backward_stop(self, st, d_hidden=None):
+        """backward_stop for the forward `st`: (lowest layer the backward visits, whether it must produce dL/d(its input))."""
+        un = self.units
+        below = un["emb"] or (un["region"] and st.img is not None) or d_hidden is not None
+        return backward_stop(un["layers"], below, None if st.hist is None else st.hist["need"])
 
     def _trunk_bwd(self, st, g32, acc, comm=None, word_grad_ready=False, d_hidden=None):
         """Back through the trunk: g32 fp32 [rows, H] = dL/d(sequence output) in the layout of the forward (st), or None
         when the caller has already put it (bf16) into bufs.g; the gradients of the encoder layers, the embeddings and the
-        region projection land in the flat slab."""
+        region projection land in the flat slab.  Frozen units are not computed, and the layer loop stops at the lowest
+        layer under which nothing wants a gradient (_backward_stop)."""
         if st.serial != self._fwd_serial:
             raise RuntimeError("the activations of this forward were overwritten by a later forward of the same engine; "
                                "run backward before the next forward")
@@ -948,8 +1143,10 @@ class PretrainEngine(object):
         emb = m.bert.embeddings
         B, T, R, S, H, L, Mr, lay = st.B, st.T, st.R, st.S, st.H, st.L, st.Mr, st.lay
         p_h, seed, ids, tt, pos_ids, img = st.p_h, st.seed, st.ids, st.tt, st.pos_ids, st.img
+        un = self.units
+        stop, need_dx = self._backward_stop(st, d_hidden)
         word_grad = self._grad(emb.word_embeddings.weight)
-        if not acc and not word_grad_ready:
+        if not acc and not word_grad_ready and self._is_trainable(emb.word_embeddings.weight):
             word_grad.zero_()
         g = bufs.g[:Mr]
         if g32 is not None:
@@ -961,7 +1158,7 @@ class PretrainEngine(object):
             raise NotImplementedError("encoder_history_states together with the chunked data-parallel backward is not served")
         if st.hist is not None or ops.profiling() or st.hs is not None:
             self._encoder_backward_unrolled(bufs, st.x_enc, st.enc_mask, g, B, S, acc, p_h, st.p_a, seed, lay, st.mask_additive,
-                                            st.hs, inject=d_hidden, hist=st.hist)
+                                            st.hs, inject=d_hidden, hist=st.hist, stop=stop, need_dx=need_dx)
         else:
             # The C loop, last layers first: all layers in one call, or
             #  * data-parallel (comm): in chunks of layers -- as soon as a chunk's kernels are enqueued its gradient ranges are
@@ -971,17 +1168,20 @@ class PretrainEngine(object):
             #    forward's layout) added to the running gradient in front of layer l's backward, d_hidden[0] (the embedding
             #    output) behind layer 0's.  (d_hidden[L] is part of g already.)
             step = 1 if d_hidden is not None else max(1, L if comm is None else int(comm["layers_per_chunk"]))
-            for hi in range(L, 0, -step):
-                lo = max(0, hi - step)
+            for hi in range(L, stop, -step):
+                lo = max(stop, hi - step)
                 if d_hidden is not None and hi < L and d_hidden[hi] is not None:
                     g.add_(d_hidden[hi])
-                self._encoder_backward_layers(st, g, acc, lo, hi)
+                self._encoder_backward_layers(st, g, acc, lo, hi, need_dx or lo > stop)
                 if comm is not None:
                     rng = self._layer_chunk_ranges(lo, hi)
                     comm["launch"](rng)
                     comm["done"].extend(rng)
             if d_hidden is not None and d_hidden[0] is not None:
                 g.add_(d_hidden[0])
+        want_reg = img is not None and un["region"]
+        if not (un["emb"] or want_reg):   # nothing under the layers is trainable: no embedding / region backward at all
+            return
         if lay is not None:   # dL/dx0 back in the padded row order (zero at the padding rows, as in the padded run)
             # gathers: padded row -> its compact row, or the zero row kept behind the compact rows (Mr < M here); the text
             # and the region positions land in two contiguous blocks (what the embedding and the region backward read)
@@ -992,6 +1192,16 @@ class PretrainEngine(object):
             g_pitch = T
         else:
             g_text, g_reg, g_pitch = g, None, S
+        if un["emb"]:
+            self._embedding_backward(st, g_text, g_pitch, acc)
+        if want_reg:
+            self._region_backward(st, g, g_reg, acc)
+
+    def _embedding_backward(self, st, g_text, g_pitch, acc):
+        """The embedding block's gradients (its LayerNorm and the three tables) from the text rows' dL/dx0."""
+        emb, bufs = self.model.bert.embeddings, st.bufs
+        B, T, H, p_h, seed, ids, tt, pos_ids = st.B, st.T, st.H, st.p_h, st.seed, st.ids, st.tt, st.pos_ids
+        word_grad = self._grad(emb.word_embeddings.weight)
         # embeddings: text rows
         de = ops.embed_layernorm_bwd(ids, tt, pos_ids, emb.word_embeddings.weight.detach(),
                                      emb.position_embeddings.weight.detach(), emb.token_type_embeddings.weight.detach(),
@@ -1016,32 +1226,38 @@ class PretrainEngine(object):
             type_grad[0].add_(pos_sum.sum(0) if pos_sum is not None else de.sum(0))
         else:
             ops.embed_table_grad(tt.reshape(-1), de, type_grad)
-        # region projection
-        if img is not None:
-            g_img = g_reg if g_reg is not None else g.view(B, S, H)[:, T:].reshape(B * R, H)
-            if p_h > 0.0:
-                ops.apply_dropout(g_img, (p_h, seed, ops.SITE_IMG))   # g is not read again after this point
-            if st.img_pre is not None:   # back through the image LayerNorm
-                ln = m.bert.LayerNorm
-                g_img = ops.layernorm_bwd(st.img_pre, g_img.contiguous(), ln.weight.detach(), ln.variance_epsilon,
-                                          self._grad(ln.weight), self._grad(ln.bias), ws=bufs.ws_t["ln_partial"],
-                                          accumulate=acc)
-            ops.wgrad([dict(dy=g_img, x=st.a_img, dw=self.dw_img, db=self.db_img)], B * R)
-            D, bt = m.bert.img_dim, m.bert   # (the K-concatenated operand's columns are the two weights' gradients)
-            for prm, src in ((bt.img_embedding.weight, self.dw_img[:, :D]), (bt.location_embeds.weight, self.dw_img[:, D:D + 128]),
-                             (bt.img_embedding.bias, self.db_img), (bt.location_embeds.bias, self.db_img)):
-                getattr(self._grad(prm), "add_" if acc else "copy_")(src)
 
-    def _encoder_backward_layers(self, st, g, acc, lo, hi):
+    def _region_backward(self, st, g, g_reg, acc):
+        """The region group's gradients from the region rows' dL/dx0 (g_reg: those rows gathered from a compacted layout)."""
+        m, bufs = self.model, st.bufs
+        B, T, R, S, H, p_h, seed = st.B, st.T, st.R, st.S, st.H, st.p_h, st.seed
+        # region projection
+        g_img = g_reg if g_reg is not None else g.view(B, S, H)[:, T:].reshape(B * R, H)
+        if p_h > 0.0:
+            ops.apply_dropout(g_img, (p_h, seed, ops.SITE_IMG))   # g is not read again after this point
+        if st.img_pre is not None:   # back through the image LayerNorm
+            ln = m.bert.LayerNorm
+            g_img = ops.layernorm_bwd(st.img_pre, g_img.contiguous(), ln.weight.detach(), ln.variance_epsilon,
+                                      self._grad(ln.weight), self._grad(ln.bias), ws=bufs.ws_t["ln_partial"],
+                                      accumulate=acc)
+        ops.wgrad([dict(dy=g_img, x=st.a_img, dw=self.dw_img, db=self.db_img)], B * R)
+        D, bt = m.bert.img_dim, m.bert   # (the K-concatenated operand's columns are the two weights' gradients)
+        for prm, src in ((bt.img_embedding.weight, self.dw_img[:, :D]), (bt.location_embeds.weight, self.dw_img[:, D:D + 128]),
+                         (bt.img_embedding.bias, self.db_img), (bt.location_embeds.bias, self.db_img)):
+            getattr(self._grad(prm), "add_" if acc else "copy_")(src)
+
+    def _encoder_backward_layers(self, st, g, acc, lo, hi, need_dx=True):
         """Layers [lo, hi) of the forward `st` through the C loop (one library call), last layer first: g, the running
-        gradient, enters as dL/d(output of layer hi - 1) and leaves as dL/d(input of layer lo)."""
+        gradient, enters as dL/d(output of layer hi - 1) and leaves as dL/d(input of layer lo) -- unless need_dx is False:
+        nothing reads it, and layer lo does not launch its last dgrad."""
         bufs = st.bufs
         sub = lambda arr, typ: (typ * (hi - lo)).from_address(ctypes.addressof(arr) + lo * ctypes.sizeof(typ))
         ops.encoder_backward(sub(self.w_tab, _lib.LayerWeights), sub(self.wt_tab, _lib.LayerWeightsT),
                              sub(bufs.acts, _lib.LayerActs), sub(self.g_tab, _lib.LayerGrads),
                              st.x_enc if lo == 0 else bufs.layers[lo - 1]["out"], st.enc_mask, st.mask_additive, g, bufs.ws,
                              st.B, st.S, st.H, st.nh, st.I, self.cfg.layer_norm_eps, accumulate=acc, p_hidden=st.p_h,
-                             p_attn=st.p_a, drop_seed=st.seed, layer0=lo, seq=st.lay, **self._overlap_kw(bufs))
+                             p_attn=st.p_a, drop_seed=st.seed, layer0=lo, seq=st.lay, need_input_grad=need_dx,
+                             **self._overlap_kw(bufs))
 
     # ------------------------------------------------------------------------------ trunk-level training
     def trunk_forward(self, batch, head_mask=None, training=None, unmasked_only=False, want_hidden=False, want_attn=False,
@@ -1055,6 +1271,7 @@ class PretrainEngine(object):
         Sh + S keys, [B, Sh+S] or per query [B, S, Sh+S]); trunk_backward then leaves their gradients in st.d_history."""
         if training is None:
             training = self.model.bert.training
+        self._sync_trainable()
         if self.precision == "fp32":
             if history:
                 raise NotImplementedError("PretrainEngine(precision='fp32') does not serve encoder_history_states")
@@ -1167,7 +1384,8 @@ class PretrainEngine(object):
         if d_pooled is not None:
             g_z = (d_pooled.detach().float() * (1.0 - st.pooled * st.pooled)).to(BF16)
             x_cls = st.seq.view(B, S * H)[:, :H] if lay is None else st.cls_seq
-            ops.wgrad([dict(dy=g_z, x=x_cls, dw=self._grad(pw), db=self._grad(pb), accumulate=acc)], B)
+            if self.units["pooler"]:
+                ops.wgrad([dict(dy=g_z, x=x_cls, dw=self._grad(pw), db=self._grad(pb), accumulate=acc)], B)
             g32.index_add_(0, st.cls_rows, ops.linear(g_z, self.head_t["pool"]).float())
         elif not acc:
             self._zero_head_grads("pooler")
@@ -1242,8 +1460,11 @@ class PretrainEngine(object):
         return dict(ws_b=bufs.ws_b, side_stream=self._side_stream)
 
     def _encoder_backward_unrolled(self, bufs, x0, mask, g, B, S, acc, p_h=0.0, p_a=0.0, seed=0, lay=None,
-                                   mask_additive=False, hs=None, inject=None, hist=None):
-        """hist (_history_state of the forward): the rectangular attention backward gives the gradient of the extended
+                                   mask_additive=False, hs=None, inject=None, hist=None, stop=0, need_dx=True):
+        """stop / need_dx (_backward_stop): the loop visits layers L-1 .. stop, and layer `stop` launches its last dgrad only
+        with need_dx (or for a history tensor's gradient); a frozen layer runs its dgrad chain, its attention backward and
+        its two LayerNorm backwards dx-only, and nothing else.
+        hist (_history_state of the forward): the rectangular attention backward gives the gradient of the extended
         projection [B*St, 3H]; one dgrad GEMM over those rows yields the hidden rows' gradient (joined with the residual
         gradient) and, in fp32, d_history[l] (kept in hist["d"] for history tensors that require grad); the packed QKV
         weight gradient is a launch of its own over the B*St rows (the dq columns of history rows are zero, so the query
@@ -1251,10 +1472,13 @@ class PretrainEngine(object):
         cfg = self.cfg
         nh, eps, M = cfg.num_attention_heads, cfg.layer_norm_eps, x0.shape[0]
         w = {k: (v[:M] if k in bufs.ws_rowed else v) for k, v in bufs.ws_t.items()}
-        for l in range(cfg.num_hidden_layers - 1, -1, -1):
+        for l in range(cfg.num_hidden_layers - 1, stop - 1, -1):
             if inject is not None and l + 1 < cfg.num_hidden_layers and inject[l + 1] is not None:
                 g.add_(inject[l + 1])   # dL/d(output of layer l) from a caller that read the intermediate hidden states
             (t, gr, wt), a = self._layers[l], bufs.layers[l]
+            train, dx = self.units["layers"][l], need_dx or l > stop
+            if not train:   # frozen: no parameter gradients from the LayerNorm backwards, no weight-gradient launch
+                gr = dict.fromkeys(gr)
             a = {k: (v if k in ("lse", "keep_bits") else v[:M]) for k, v in a.items()}
             x_in = x0 if l == 0 else bufs.layers[l - 1]["out"][:M]
             hd = p_h > 0.0   # with hidden dropout the dense outputs' gradients are the masked copies
@@ -1281,18 +1505,22 @@ class PretrainEngine(object):
                 g_ext = ops.attention_rect_bwd(hist["qkv"][l], g_ctx, ctx_l, a["lse"], B, S, St, nh, mask=mask,
                                                mask_additive=mask_additive, drop=(p_a, seed, ops.site_attn(l)),
                                                keep_bits=hist["keep"][l] if p_a > 0.0 else None)
-                gx = ops.linear(g_ext, wt["wt_qkv"], out_f32=True).view(B, St, H)
-                g.copy_((gx[:, Sh:] + w["g_pre2"].view(B, S, H).float()).reshape(M, H))
-                if hist["need"][l]:
-                    hist["d"][l] = gx[:, :Sh].clone()
-                ops.wgrad([prob(g_ext, hist["xs"][l], "qkv")], B * St)
-                ops.wgrad(ffn + [ao], M)
+                if dx or hist["need"][l]:
+                    gx = ops.linear(g_ext, wt["wt_qkv"], out_f32=True).view(B, St, H)
+                    g.copy_((gx[:, Sh:] + w["g_pre2"].view(B, S, H).float()).reshape(M, H))
+                    if hist["need"][l]:
+                        hist["d"][l] = gx[:, :Sh].clone()
+                if train:
+                    ops.wgrad([prob(g_ext, hist["xs"][l], "qkv")], B * St)
+                    ops.wgrad(ffn + [ao], M)
                 continue
             ops.attention_bwd(a["qkv"], g_ctx, ctx_l, a["lse"], B, S, nh, mask=mask, mask_additive=mask_additive,
                               out=w["g_qkv"], delta_ws=w["delta"], dq32_ws=w.get("dq32"), drop=(p_a, seed, ops.site_attn(l)),
                               seq=lay, keep_bits=a.get("keep_bits") if p_a > 0.0 else None)
-            ops.linear(w["g_qkv"], wt["wt_qkv"], residual=w["g_pre2"], out=g)
-            ops.wgrad(ffn + [prob(w["g_qkv"], x_in, "qkv"), ao], M)
+            if dx:
+                ops.linear(w["g_qkv"], wt["wt_qkv"], residual=w["g_pre2"], out=g)
+            if train:
+                ops.wgrad(ffn + [prob(w["g_qkv"], x_in, "qkv"), ao], M)
         if inject is not None and inject[0] is not None:
             g.add_(inject[0])           # ... and with respect to the embedding output
 
@@ -1309,33 +1537,61 @@ class PretrainEngine(object):
                 "PretrainEngine(model) and carry the optimizer state over with state_dict() / load_state_dict()")
 
     def _adam_begin(self):
-        """Advance Adam's step counter and return this step's constants (lr after the schedule, bias-corrected step size)."""
+        """Advance Adam's step counter -- the global one and every trainable parameter's own -- and return this step's
+        constants (lr after the schedule, the step size bias-corrected for a parameter updated at every step so far)."""
         self._require_ownership()
+        self._sync_trainable()
         self.step_count += 1
-        t = self.step_count
+        for n, fl in self._trainable.items():
+            if fl:
+                self.param_steps[n] += 1
+        self.adam_segments = [(s_, e_, t + 1) for s_, e_, t in self.adam_segments]
         lr = self.lr * self.lr_factor()
         b1, b2 = self.betas
-        step_size = lr
-        if self.correct_bias:
-            step_size = lr * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
-        return lr, step_size, b1, b2
+        return lr, self._step_size(lr, self.step_count), b1, b2
+
+    def _adam_abort(self):
+        """Take back _adam_begin's counting: no update was completed on behalf of the step."""
+        self.step_count -= 1
+        for n, fl in self._trainable.items():
+            if fl:
+                self.param_steps[n] -= 1
+        self.adam_segments = [(s_, e_, t - 1) for s_, e_, t in self.adam_segments]
+
+    def _step_size(self, lr, t):
+        """lr with Adam's bias correction after t updates."""
+        if not self.correct_bias:
+            return lr
+        b1, b2 = self.betas
+        return lr * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
 
     def _adam_ranges(self, consts, ranges, grad_scale, grads=None):
-        """The fused AdamW on [start, end) ranges of the flat slabs (weight decay by region: pretrain.py:109-127)."""
+        """The fused AdamW on the trainable parts of [start, end) ranges of the flat slabs (weight decay by region:
+        pretrain.py:109-127), each segment with the bias correction of its own update count."""
         f = self.flat
-        lr, step_size, b1, b2 = consts
+        lr, _, b1, b2 = consts
         g = f.g if grads is None else grads   # fp32 slab, or the all-reduced bf16 communication copy
         nd = f.n_decay
         for s_, e_ in ranges:
-            for lo, hi, wd in ((s_, min(e_, nd), self.wd), (max(s_, nd), e_, 0.0)):
-                if hi > lo:
-                    ops.adamw_flat(f.p[lo:hi], g[lo:hi], f.m[lo:hi], f.v[lo:hi], f.mirror[lo:hi], lr, step_size, b1, b2,
-                                   self.eps, wd, grad_scale)
+            for a_, b_, t in self.adam_segments:
+                s0, e0 = max(s_, a_), min(e_, b_)
+                if e0 <= s0:
+                    continue
+                step_size = self._step_size(lr, t)
+                for lo, hi, wd in ((s0, min(e0, nd), self.wd), (max(s0, nd), e0, 0.0)):
+                    if hi > lo:
+                        ops.adamw_flat(f.p[lo:hi], g[lo:hi], f.m[lo:hi], f.v[lo:hi], f.mirror[lo:hi], lr, step_size, b1, b2,
+                                       self.eps, wd, grad_scale)
 
     def _adam_end(self):
         self.sched_step += 1
         self.flat.mark_fresh()
-        self._wt_dirty = True
+        # the transposed copies of what AdamW just stepped are stale (a pending full rebuild stays one; two steps under
+        # different flags without a forward between them: everything)
+        if self._wt_dirty is False:
+            self._wt_dirty = self._flags
+        elif self._wt_dirty != self._flags:
+            self._wt_dirty = True
         # the fused kernel wrote the slab through raw pointers: no parameter's _version moved, so the packed bf16
         # copies the inference path caches (encoder layers, region projection, rollout modules) are told explicitly
         invalidate_packed_weights()
@@ -1375,7 +1631,7 @@ class PretrainEngine(object):
             comm = dict(layers_per_chunk=layers_per_chunk, launch=launch, done=[])
             out = self.forward_backward(batch, grad_scale=scale, comm=comm)
         except BaseException:
-            self.step_count -= 1   # no update was completed on behalf of this step's counter
+            self._adam_abort()   # no update was completed on behalf of this step's counters
             torch.cuda.current_stream().wait_stream(side)
             raise
         self._adam_ranges(consts, distributed.complement_ranges(self.flat.total, comm["done"]), 1.0)
@@ -1571,6 +1827,8 @@ class PretrainEngine(object):
                  for n, _, _, _, _ in f.entries}
         return dict(state=state, step_count=self.step_count, sched_step=self.sched_step, fb_count=self.fb_count,
                     drop_seed_base=self.drop_seed_base,
+                    # updates per parameter (they differ once requires_grad changed during the run)
+                    param_steps=dict(self.param_steps),
                     hyper=dict(lr=self.lr, weight_decay=self.wd, eps=self.eps, betas=tuple(self.betas),
                                correct_bias=self.correct_bias, schedule=self.schedule, warmup_steps=self.warmup_steps,
                                t_total=self.t_total,
@@ -1599,6 +1857,10 @@ class PretrainEngine(object):
                     sh[mo:mo + e_ - s_].copy_(full[s_:e_])
         self.step_count, self.sched_step = int(sd["step_count"]), int(sd["sched_step"])
         self.fb_count, self.drop_seed_base = int(sd["fb_count"]), int(sd["drop_seed_base"])
+        # a state without per-parameter counts (written before they existed): every parameter from the global step
+        steps = sd.get("param_steps")
+        self.param_steps = {n: int(self.step_count if steps is None else steps[n]) for n, _, _, _, _ in f.entries}
+        self._rebuild_segments()
         if load_hyper:
             h = sd["hyper"]
             self.lr, self.wd, self.eps, self.betas = h["lr"], h["weight_decay"], h["eps"], tuple(h["betas"])
@@ -1612,7 +1874,12 @@ class PretrainEngine(object):
         if self.shard:
             raise RuntimeError("with the optimizer sharded over the ranks no rank holds the whole reduced gradient slab: call "
                                "optimizer_step(), which reduce-scatters, updates and gathers")
-        distributed.all_reduce_flat(*self._comm_copy([(0, self.flat.total)]), self.pg)
+        self._sync_trainable()
+        if all(self._flags):
+            distributed.all_reduce_flat(*self._comm_copy([(0, self.flat.total)]), self.pg)
+            return
+        buf, per_bucket = self._comm_copy(self.train_spans)   # frozen ranges stay off the wire
+        distributed.all_reduce_ranges(buf, self.train_spans, per_bucket, self.pg)
 
     def train_step(self, batch, overlap=True, layers_per_chunk=3, _force_comm=None):
         """zero_grad -> forward -> backward -> gradient all-reduce -> AdamW -> schedule, as pretrain.py:150-193.
@@ -1644,7 +1911,8 @@ class PretrainEngine(object):
             launch = _force_comm or reduce_ranges
             comm = dict(layers_per_chunk=layers_per_chunk, launch=launch, done=[])
             out = self.forward_backward(batch, grad_scale=scale, comm=comm)
-            launch(distributed.complement_ranges(self.flat.total, comm["done"]))  # embeddings, region projection, heads
+            # embeddings, region projection, heads (and whatever is frozen, which is not reduced)
+            launch(self._trainable_ranges(distributed.complement_ranges(self.flat.total, comm["done"])))
             if _force_comm is None:
                 # AdamW per arrived range, in launch order (last layers first, the embeddings / heads tail last): the update
                 # of the encoder's 85 M parameters runs while the tail's all-reduce is still in flight.  (wait() makes this
