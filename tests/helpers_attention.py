@@ -342,11 +342,12 @@ class BackwardTerms(object):
 
 # Where the dropout scale meets the rounding of dS (both are minimal: ONE rounding of dS; 1 - p is no power of two, so the two
 # forms round the same dS to different bf16 values and their errors are different draws of the same size):
-#   "folded"    dS / (8 (1 - p)) ... is rounded with every scale folded in: csrc/attention_bwd.hip, the 4-wave kernel
+#   "folded"    dS / (8 (1 - p)) ... is rounded with every scale folded in: csrc/attention_bwd_keyblock.hip, the 4-wave kernel
 #               (`sacc[i] = p * (dpv - del4[g4][e]) * ds_scale;  // dS' (scales folded in)`)
 #   "deferred"  P (keep dP_raw - delta (1 - p)) = (1 - p) dS is rounded, and ds_scale = 1 / (8 (1 - p)) multiplies the fp32 dK / dQ
-#               accumulators afterwards: the 8-wave kernel and both 16-wave kernels (`sacc[i] = p * (dpv - del4_g[e]);   // dS'
-#               up to ds_scale`, `dsv[4 * t + j] = p * (dpv - e4[j]);`)
+#               accumulators afterwards: the 8-wave kernel (the same file) and both 16-wave kernels (attention_bwd_w16.hip,
+#               attention_bwd_w16p.hip) (`sacc[i] = p * (dpv - del4_g[e]);   // dS' up to ds_scale`,
+#               `dsv[4 * t + j] = p * (dpv - e4[j]);`)
 # Without dropout the two coincide.  Measured on an MI355X before the forms were told apart: every kernel's dV and the 4-wave
 # kernel's dQ / dK reproduce the "folded" model's error exactly (max ratio 0.333 = 1 / 3), the other kernels' dQ / dK under
 # dropout are the other draw (L2 within 1.12 x the model's; one element of 4 224 in one (batch, head) of a 256-sequence sweep one

@@ -99,7 +99,7 @@ def test_generated_wgrad_step_is_current():
 
 
 def test_attention_kernels_register_budgets_and_the_writelane_hazard(tmp_path):
-    """attention_fwd.hip / attention_bwd.hip: the forward must stay within 128 VGPRs (two 8-wave workgroups per CU, four
+    """attention_fwd.hip / attention_bwd_*.hip: the forward must stay within 128 VGPRs (two 8-wave workgroups per CU, four
     waves per SIMD: the kernel is bound by vector issue and lives on that occupancy), the inference instantiation without
     scratch; the backward without scratch.  The training forward moves each compare's lane mask into the lane of its key
     with v_writelane_b32 from inline asm: hipcc's hazard recognizer does not see into the statement, and without wait states
@@ -125,9 +125,16 @@ def test_attention_kernels_register_budgets_and_the_writelane_hazard(tmp_path):
                     j -= 1
                 m = re.match(r"s_nop (\d+)", lines[j])
                 assert m and int(m.group(1)) >= 4, (name, lines[j])
-    ks = _kernels(_device_asm(os.path.join(CSRC, "attention_bwd.hip"), tmp_path))
-    bwd = {n: t for n, t in ks.items() if "attention_bwd_d64" in n}
-    # 4 waves; 8 waves x (hash | keep words) x (delta pass | in-kernel); 16 waves and 16 waves persistent, each x (keep words | none)
+    # one file per kernel family: 4 waves + 8 waves x (hash | keep words) x (delta pass | in-kernel); 16 waves and 16 waves
+    # persistent, each x (keep words | none).  attention_bwd.hip itself keeps the dispatcher and the small kernels around it.
+    bwd = {}
+    for src, count in (("attention_bwd_keyblock.hip", 5), ("attention_bwd_w16.hip", 2), ("attention_bwd_w16p.hip", 2),
+                       ("attention_bwd.hip", 0)):
+        ks = _kernels(_device_asm(os.path.join(CSRC, src), tmp_path))
+        fam = {n: t for n, t in ks.items() if "attention_bwd_d64" in n}
+        assert len(fam) == count, (src, sorted(fam))
+        assert ("w16p" in src) == any("w16p" in n for n in fam) and ("w16" in src) == any("w16" in n for n in fam), src
+        bwd.update(fam)
     assert len(bwd) == 9
     for name, text in bwd.items():
         assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", text).group(1)) == 0, name

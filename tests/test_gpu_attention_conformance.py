@@ -1,5 +1,5 @@
-"""The fused attention kernels (csrc/attention_fwd.hip, csrc/attention_bwd.hip) against the fp64 reference and the derived
-bounds of tests/helpers_attention.py, through visitron_amd.ops only.  This file is the acceptance gate of any new attention
+"""The fused attention kernels (csrc/attention_fwd.hip; csrc/attention_bwd.hip and its kernel files attention_bwd_*.hip)
+against the fp64 reference and the derived bounds of tests/helpers_attention.py, through visitron_amd.ops only.  This file is the acceptance gate of any new attention
 kernel; alone:  python -m pytest tests/test_gpu_attention_conformance.py -q -s
 
 Every case runs the forward (with lse), the probabilities where the layout allows them (padded, no dropout) and the backward

@@ -37,7 +37,7 @@ _cases = {}
 def _case(dev, S, layout, drop):
     """One forward at B = 2, nh = 2 (kept per (S, layout, drop): every test below reads the same inputs and the same fp64
     reference).  layout "masked": padded rows, a raw key mask that masks sequence 1's whole last key block (and three keys of
-    sequence 0); "seq": compacted rows of lengths {S, 300}; "plain": padded, no mask."""
+    sequence 0); "seq": compacted rows of lengths {S, 300} ({S, 200} where S <= 300); "plain": padded, no mask."""
     from visitron_amd import ops
 
     key = (S, layout, drop)
@@ -55,7 +55,7 @@ def _case(dev, S, layout, drop):
         mask[0, 5:8] = 0
         bias = ((1.0 - mask) * -10000.0).to(ha.F64)
     elif layout == "seq":
-        lens = [S, 300]
+        lens = [S, 300 if S > 300 else 200]
         keepm = torch.arange(S)[None, :] < torch.tensor(lens)[:, None]
         seq = ops.SeqLayout(keepm.to(dev))
         index = seq.index.cpu()
@@ -95,11 +95,12 @@ def _case(dev, S, layout, drop):
     return c
 
 
-def _bwd(c, ws=None):
+def _bwd(c, ws=None, hash_keep=False):
+    """hash_keep: the backward gets no keep words and re-derives the forward's decisions from the hash."""
     from visitron_amd import ops
 
-    out = ops.attention_bwd(c["qd"], c["dd"], c["ctx"], c["lse"], c["B"], c["S"], NH, drop=c["dr"], keep_bits=c["words"],
-                            dq32_ws=ws, **c["kw"])
+    out = ops.attention_bwd(c["qd"], c["dd"], c["ctx"], c["lse"], c["B"], c["S"], NH, drop=c["dr"],
+                            keep_bits=None if hash_keep else c["words"], dq32_ws=ws, **c["kw"])
     torch.cuda.synchronize()
     return out
 
@@ -159,6 +160,41 @@ def test_one_and_two_key_blocks_keep_their_bits(dev, det, S):
         off = _bwd(c)
         det.set_deterministic(True)
         assert torch.equal(on, off), "S=%d drop=%s" % (S, drop)
+
+
+@pytest.mark.parametrize("drop", ["none", "keep words", "hash"])
+@pytest.mark.parametrize("layout", ["masked", "seq"])
+@pytest.mark.parametrize("waves", [4, 8, 10])
+def test_every_key_block_kernel_under_the_switch(dev, det, waves, layout, drop):
+    """The tests above run the default setting, which from two key blocks on is the 8-wave kernel forming delta itself, with keep
+    words.  set_attn_bwd_waves 4 (the 4-wave kernel), 8 and 10 (the 8-wave kernel with delta in the kernel / from the separate
+    pass), each without dropout, with the forward's keep words and with the decisions re-derived from the hash, reach every
+    plane-storing instantiation.  S = 257 is the shortest length with two key blocks, the second of one key; in the compacted
+    batch the second sequence has 200 rows, so key block 1 of it lies past its end and must store zeros.  Held to: the fp64
+    reference with the margins of tests/helpers_attention.py; dq = bf16(p0 + p1) from a NaN-filled workspace; a second launch
+    (library-sized workspace) with the same bits."""
+    import test_gpu_attention_conformance as conf
+
+    S = 257
+    c = _case(dev, S, layout, drop != "none")
+    rows, hash_keep = c["rows"], drop == "hash"
+    ws = torch.full((2 * rows * H,), float("nan"), device=dev)
+    det.set_attn_bwd_waves(waves)
+    try:
+        out = _bwd(c, ws, hash_keep)
+        again = _bwd(c, None, hash_keep)
+    finally:
+        det.set_attn_bwd_waves(0)
+    planes = ws.view(2, rows, H)
+    assert not bool(torch.isnan(planes).any()), "a (plane, row) the kernels did not write"
+    assert torch.equal(out[:, :H], (planes[0] + planes[1]).to(BF16))
+    if layout == "seq":    # key 256 does not exist for the 200-row sequence: its rows of plane 1 are zeros
+        assert rows == S + 200 and float(planes[1, S:].abs().max()) == 0.0
+    assert torch.equal(again, out), "two launches differ"
+    gp = c["padded"](out)
+    got = tuple(ha.heads(gp[:, i * H:(i + 1) * H], c["B"], S, NH) for i in range(3))
+    ratios = ha.backward_ratios(c["get_terms"](), got, lens=c["lens"], ds_form=conf.DS_FORM[waves])
+    ha.assert_ratios("deterministic bwd waves %d S=%d %s %s" % (waves, S, layout, drop), ratios)
 
 
 # ---- persistent weight gradient ------------------------------------------------------------------------------------------------

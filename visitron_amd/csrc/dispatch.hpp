@@ -20,7 +20,8 @@ struct BatchRowsArgs {
   long n_w, n_t, n_keep;                // capacities of the three lists (the counts batch_row_counts reported)
 };
 
-// ---- attention_bwd.hip
+// ---- attention_bwd.hip: the dispatcher and its route (the kernel families' launchers: attention_bwd_common.hpp, one each
+// for attention_bwd_keyblock.hip, attention_bwd_w16.hip and attention_bwd_w16p.hip)
 void vt_attn_bwd_set_waves(int w);
 int vt_attention_bwd_dispatch(const void* qkv, long ld_qkv, const void* dctx, long ld_d, const void* ctx, long ld_ctx,
                               const float* mask, int mask_additive, const float* lse, float* delta_ws, void* dqkv,
